@@ -15,16 +15,24 @@ collective is the obs all-gather.
 
 The regime is fixed by the bench, not by --steps / --warmup: PREROLL untimed control steps run first (the population of
 standing / falling / freshly reset robots is stationary after ~100 control steps), then --warmup, then the timed region.
-After the timed region a sampling pass of SAMPLE_LAUNCHES more control steps of the same sequence is run with every
+
+A plain single-GPU run (no --full) does only what `value` needs: set-up, pre-roll, --warmup control steps through the leg `value`
+reports (one resident launch of max(1, --warmup) steps), ONE timed bracket of exactly --steps control steps of that leg, the outputs of its
+last control step if --dump-outputs DIR is given (DIR/obs.npy, done.npy, gc.npy, gv.npy), and the JSON line.  Everything below -
+the other legs, brackets of 7 repeats, the sampling pass, `roofline`, the CPU baseline, `secondary`, `closed_loop`,
+`boundary_template_path` - runs with --full.  A run with several ranks (or --force-collective) without --full keeps its legs (lock-step
+first, pipelined, resident; one bracket each) and drops the sampling pass, the trailing lock-step leg and the CPU leg.
+
+With --full, after the timed region a sampling pass of SAMPLE_LAUNCHES more control steps of the same sequence is run with every
 launch bracketed by HIP events on the launch stream (inside the library), so the kernel duration behind `roofline` never
 rests on a handful of brackets; the few brackets taken inside the timed region (every EVENT_STRIDE-th launch) are reported
 next to it.  The same pass counts resets per step and the env-age distribution (config.workload).
 
-Output: ONE JSON line on rank 0 with `roofline` (HBM; SURVEY.md §8d algorithmic bytes per env-step x env-steps per launch
+Output: ONE JSON line on rank 0; with --full it carries `roofline` (HBM; SURVEY.md §8d algorithmic bytes per env-step x env-steps per launch
 over the step kernel's mean launch duration) and `cpu_baseline` (the in-repo fp64 oracle, OpenMP over envs on the host
 cores, started from the GPU population's state at the start of the timed region; rank 0, N=1 only).
 
-What else the default single-GPU line carries (round 4-5):
+What else the default single-GPU --full line carries (round 4-5):
   value / lockstep      the timed region with consecutive control steps pipelined on the device (rsb_set_step_pipelining) and, same bracket,
                         with every launch waiting for the one before it; roofline.frac_throughput / frac_kernel_duration say which time each
                         fraction divides by; below 64 steps every launch of the timed region is bracketed (stride 1)
@@ -76,7 +84,7 @@ def parse():
     ap.add_argument("--slip-rule", default="energy", choices=("energy", "coulomb"), help="diagnostic: rsb_set_slip_rule (coulomb = the classical law, a kernel class of its own)")
     ap.add_argument("--anderson", type=int, default=-1, help="diagnostic: first sweep of the Anderson step in multi-contact envs of kmax > 8 worlds (library default 2; 0 = off)")
     ap.add_argument("--no-reset", action="store_true", help="disable the non-foot-contact termination rule")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg (--full)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--stall-window", type=int, default=-1, help="diagnostic: solver stagnation window (library default 4)")
     ap.add_argument("--freeze-after", type=int, default=-1, help="diagnostic: sweeps before friction directions lag (default 6)")
@@ -106,10 +114,19 @@ def parse():
                          "this number as `lockstep` next to the pipelined `value`")
     ap.add_argument("--no-secondary", action="store_true",
                     help="headline only: skip the `secondary` block (configs 3 and 5 with the same --steps / --warmup) and `boundary_template_path` "
-                         "that the default single-GPU run of config 2 appends")
-    ap.add_argument("--repeats", type=int, default=7,
+                         "that the default single-GPU --full run of config 2 appends")
+    ap.add_argument("--repeats", type=int, default=None,
                     help="every timed leg is R fresh brackets of exactly --steps steps, back to back; `value` = the MEDIAN bracket, value_repeats / value_min / "
-                         "value_max beside it (VERDICT r05 #2: a 1.7 ms region measured once is not a measurement)")
+                         "value_max beside it (VERDICT r05 #2: a 1.7 ms region measured once is not a measurement).  Default 7 with --full, else 1: "
+                         "a plain run times exactly --steps steps (--closed-loop-only: 7)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything the benchmark measures besides the headline: the other legs (pipelined, lock-step) with 7 brackets each, the sampling "
+                         "pass behind `roofline`, the CPU baseline, and on the default single-GPU line `secondary`, `closed_loop` and `boundary_template_path`.  "
+                         "Without it a single-rank run sets up, warms up, times the --steps steps of the leg `value` reports and prints the line; a run with several "
+                         "ranks (or --force-collective) keeps its legs, one bracket each, and drops the sampling pass, the trailing lock-step leg and the CPU leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed leg computed in its last control step as DIR/<name>.npy (float32): obs (the "
+                         "observation block), done (termination flags), gc / gv (generalized coordinates / velocities); a seeded sample of envs above 64 MB; with several ranks, rank 0's envs")
     ap.add_argument("--specialization", default="compile", choices=("compile", "cached", "off"),
                     help="specialised code objects of the step kernel (rsb_set_specialization; csrc/step_spec.h): compile = a key build() did not prebuild is compiled during "
                          "warm-up (~3 s, never inside a timed region); cached = prebuilt objects only; off = the ahead-of-time kernel classes (rounds 1-5)")
@@ -725,8 +742,13 @@ def measure(args, rank, local_rank, world_size, dev, coll):
             step_fns = [world.control_step_plan(workload.SUBSTEPS, o.data_ptr() if o is not None else 0, feet_idx, feet_idx if reset else None,
                                                 gc0_d.data_ptr() if reset else 0, gv0_d.data_ptr() if reset else 0, N) for o in obs_b]
             drain = gath.drain
+    # a plain run (no --full, one rank) times only the leg `value` reports: the resident leg where the world has a resident launch, else the per-step leg.
+    # Its --warmup control steps then run through that leg (a resident launch of --warmup steps), after the pre-roll
+    resident_wanted = not (args.no_resident or args.lockstep or args.obs_exchange == "peer" or args.early_termination or args.overlap_collective)
+    lean = not args.full and not coll
+    lean_resident = lean and resident_wanted and world.residency_status(0)
     kstep = 0
-    for _ in range(args.preroll + args.warmup):
+    for _ in range(args.preroll + (0 if lean_resident else args.warmup)):
         control_step(kstep)
         if reset:
             track_ages()
@@ -795,7 +817,7 @@ def measure(args, rank, local_rank, world_size, dev, coll):
         return {"value_repeats": v, "value_min": min(v), "value_max": max(v), "repeats": len(v), "spread_rel": (max(v) - min(v)) / float(np.median(v))}
 
     def start_brackets():
-        if args.no_kernel_events:
+        if args.no_kernel_events or not args.full:
             return 0
         stride = EVENT_STRIDE if args.steps >= 64 else 1      # (>= 16 brackets at the driver's --steps 20; a bracket costs ~7 us of stream time, stated in the line)
         n = R * ((args.steps + stride - 1) // stride)
@@ -819,6 +841,8 @@ def measure(args, rank, local_rank, world_size, dev, coll):
             kstep += 1
         g2.drain()
         r = repeated(per_step(step_inline), g2.drain)
+        if args.dump_outputs:
+            snap["first"] = last_step_outputs(world, g2.local(kstep - 1), done_d if reset else None)
         if g2.active:      # this rank's slice of the gathered block of the last step = its own block
             r["gathered_rows_of_this_rank_correct"] = bool(torch.equal(g2.gathered(kstep - 1)[rank * N:(rank + 1) * N], g2.local(kstep - 1)))
         r["obs_all_gather"] = g2.describe()
@@ -839,6 +863,8 @@ def measure(args, rank, local_rank, world_size, dev, coll):
             step_start = kstep
         n_in = start_brackets()
         r = repeated(per_step(control_step), drain)
+        if args.dump_outputs:
+            snap["second"] = last_step_outputs(world, gath.local_bufs[gath.slot(kstep - 1)], done_d if reset else None)
         if gath.active and hasattr(gath, "gathered"):      # this rank's slice of the gathered block of the last step = its own block
             torch.cuda.synchronize()
             r["gathered_rows_of_this_rank_correct"] = bool(torch.equal(gath.gathered(kstep - 1)[rank * N:(rank + 1) * N], gath.local(kstep - 1)))
@@ -850,6 +876,7 @@ def measure(args, rank, local_rank, world_size, dev, coll):
     # all-gathered ONCE behind it ([steps, N, obs] per rank - one larger collective instead of --steps small ones).  Bit-identical to the lock-step
     # steps (tests/test_gpu_resident.py).  Runs under the same guard as the pipelined leg when N > 1.
     res_state = {"launch_ms": np.zeros(0), "gather": None}
+    snap = {}           # --dump-outputs: the last control step's outputs of each leg, taken right after its timed brackets
 
     def leg_resident():
         nonlocal kstep
@@ -870,23 +897,28 @@ def measure(args, rank, local_rank, world_size, dev, coll):
             if coll:
                 world.get_stream()
                 dist.all_gather_into_tensor(obs_all.view(world_size * args.steps * N, obs_dim), obs_r.view(args.steps * N, obs_dim))
-        for _ in range(2):           # untimed: two launches of the same length (the population is already stationary)
-            run(kstep, args.steps)
-            kstep += args.steps
+        # untimed: two launches of the same length (the population is already stationary); a plain run: one launch of --warmup steps (at least one
+        # step, so that the resident class's first-launch cost - code-object load, a compile on a cache miss - never lands in the timed bracket)
+        for n_warm in ([max(1, args.warmup)] if lean else [args.steps, args.steps]):
+            run(kstep, n_warm)
+            kstep += n_warm
         torch.cuda.synchronize()
-        if not args.no_kernel_events:
+        events = args.full and not args.no_kernel_events
+        if events:
             world.enable_timing(max(R, 2))
             world.set_timing_stride(1)
         l0 = world.residency_launches()
         r = repeated(run, lambda: None)
         assert world.residency_launches() - l0 == R, "the resident leg did not run resident launches"
-        if not args.no_kernel_events:
+        if events:
             res_state["launch_ms"] = world.read_kernel_ms(R).astype(np.float64)
             world.enable_timing(0)
         if coll:
             r["gathered_rows_of_this_rank_correct"] = bool(torch.equal(obs_all[rank], obs_r))
             res_state["gather"] = {"collective": "all_gather_into_tensor (RCCL) ONCE per resident launch", "bytes_per_rank": int(obs_r.numel() * 4),
                                    "block": [args.steps, N, obs_dim], "issued_on": "the launch stream, behind the launch"}
+        if args.dump_outputs:
+            snap["resident"] = last_step_outputs(world, obs_r[args.steps - 1] if coll else obs_r, done_d if reset else None)
         world.set_step_residency(False)
         return r
 
@@ -905,6 +937,54 @@ def measure(args, rank, local_rank, world_size, dev, coll):
         """gathered_rows_of_this_rank_correct of a leg -> also ..._on_all_ranks (MIN over the ranks: rank 0 prints the line)"""
         if r is not None and coll and r.get("gathered_rows_of_this_rank_correct") is not None:
             r["gathered_rows_correct_on_all_ranks"] = all_agree(bool(r["gathered_rows_of_this_rank_correct"]))
+
+    def spec_block():
+        spec_mode, spec_n, gen_n = world.specialization_status()
+        return {"mode": ("off", "cached", "compile")[spec_mode], "step_launches_specialized": spec_n, "step_launches_generic": gen_n,
+                "what": "specialised code objects of the step kernel (raisimlib_amd/csrc/step_spec.h): the SAME kernel class compiled with the model's dimensions and the world's "
+                        "switches as compile-time constants; results bit-identical to the ahead-of-time class (tests/test_gpu_spec.py); counts are this world's launches of all legs"}
+
+    workload_text = (recipe.name + ", dt=0.0025, 4 sub-steps per control step fused in one launch"
+                     + (", non-foot contact -> reset (rsg_anymal rule)" if reset else ", no resets")
+                     + (", EARLY TERMINATION at the sub-step of the first non-foot contact (not upstream's rule)" if args.early_termination else "")
+                     + ", obs (q,u,foot force) written each control step"
+                     + f"; stationary regime: {args.preroll} untimed pre-roll control steps before --warmup")
+
+    def state_at_end():
+        iters = world.get_solver_iterations()
+        counts, _ = world.get_contacts()
+        q_end, _ = world.get_state()
+        return {"solver_iters_mean": float(iters.mean()), "solver_iters_max": int(iters.max()),
+                "contacts_per_env": float(counts.mean()), "base_height_mean": float(q_end[:, 2].mean())}
+
+    if lean:
+        # ---- a plain run: the leg `value` reports and nothing else (the other legs, the sampling pass behind `roofline` and the CPU leg: --full)
+        leg = leg_resident() if lean_resident else leg_primary()
+        total_env_steps = N * workload.SUBSTEPS * args.steps
+        out = {
+            "metric": recipe.metric,
+            "value": total_env_steps / leg["elapsed"], "unit": "env-steps/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": leg["elapsed"] / args.steps * 1e3, "ms_per_step_by_rank": leg["ms_by_rank"], "higher_is_better": True, "scaling": "weak",
+            **spread(leg, total_env_steps),
+            "value_is": "the MEDIAN of `repeats` fresh brackets of exactly --steps control steps each (barrier + synchronise on both sides, MAX over ranks), back to back",
+            "value_leg": "resident" if lean_resident else "pipelined" if pipelined else "lockstep",
+            "resident_leg_error": None if lean_resident or not resident_wanted else "RuntimeError: no resident kernel class for this configuration",
+            "specialization": spec_block(),
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": False,
+            "config": {"workload": workload_text, "workload_version": 3,
+                       "regime_name": (args.atlas_regime if args.config == 5 else "reset-on-non-foot-contact" if reset else "no-reset"),
+                       "preroll_control_steps": args.preroll, "envs_per_gpu": N, "substeps_per_step": workload.SUBSTEPS,
+                       "lanes_per_env": world.lanes_per_env(), "parallelism": "env-shard x1",
+                       "warmup": (f"{max(1, args.warmup)} control steps in one resident launch after the pre-roll" if lean_resident else
+                                  f"{args.warmup} control steps after the pre-roll")},
+            "build": {"source_hash": world.L.rsb_source_hash().decode(), "library": os.path.relpath(os.path.realpath(__import__("raisimlib_amd")._capi.LIB_PATH), ROOT)},
+            "host_enqueue_ms_per_step": leg["t_enqueued"] / args.steps * 1e3,
+            "state_at_end": state_at_end(),
+        }
+        if args.dump_outputs:
+            out["outputs"] = dump_outputs(args.dump_outputs, snap["resident" if lean_resident else "second"])
+        world.close()
+        return out
 
     legs = two_legs(leg_lockstep_inline if lockstep_first_wanted else None, leg_primary, all_agree)
     lockstep_first = legs["first"]
@@ -929,7 +1009,7 @@ def measure(args, rank, local_rank, world_size, dev, coll):
 
     # ---- the resident leg, under a guard (N > 1: every rank agrees whether it counts; a leg that raised anywhere counts nowhere)
     res_leg, resident_leg_error = None, None
-    if not (args.no_resident or args.lockstep or args.obs_exchange == "peer" or args.early_termination or args.overlap_collective):
+    if resident_wanted:
         try:
             res_leg = leg_resident()
         except Exception as e:
@@ -943,13 +1023,14 @@ def measure(args, rank, local_rank, world_size, dev, coll):
             resident_leg_error = resident_leg_error or "the leg raised on another rank"
         rows_ok_everywhere(res_leg)
 
-    # ---- sampling pass (untimed, same sequence continued): every launch bracketed; resets and env ages recorded
+    # ---- sampling pass (untimed, same sequence continued; --full): every launch bracketed; resets and env ages recorded
     kernel_ms_s = np.zeros(0)
     resets = []
-    if not args.no_kernel_events:
+    sampled = SAMPLE_LAUNCHES if args.full else 0
+    if sampled and not args.no_kernel_events:
         world.enable_timing(SAMPLE_LAUNCHES)
         world.set_timing_stride(1)
-    for _ in range(SAMPLE_LAUNCHES):
+    for _ in range(sampled):
         control_step(kstep)
         if reset:
             track_ages()                    # (joins: the sampling pass's launches do not overlap, their brackets are the kernel's own duration)
@@ -960,7 +1041,7 @@ def measure(args, rank, local_rank, world_size, dev, coll):
     drain()
     torch.cuda.synchronize()
     bracket_overhead_ms = None
-    if not args.no_kernel_events:
+    if sampled and not args.no_kernel_events:
         kernel_ms_s = world.read_kernel_ms(SAMPLE_LAUNCHES).astype(np.float64)
         world.enable_timing(0)
         # what an event pair measures with nothing in between, on the same stream: subtracted from the brackets
@@ -971,11 +1052,11 @@ def measure(args, rank, local_rank, world_size, dev, coll):
         torch.cuda.synchronize()
         bracket_overhead_ms = float(np.median([e0.elapsed_time(e1) for e0, e1 in evs]))
 
-    # ---- the same workload with every launch waiting for the one before it (rsb_set_step_pipelining off): same bracket, same number of steps
+    # ---- the same workload with every launch waiting for the one before it (rsb_set_step_pipelining off; --full): same bracket, same number of steps
     lockstep, lockstep_leg = None, lockstep_first
     if lockstep_first is not None:
         lockstep = lockstep_first["elapsed"]
-    elif pipelined:
+    elif pipelined and args.full:
         world.set_step_pipelining(False)
         for _ in range(max(5, args.warmup // 4)):
             control_step(kstep)
@@ -997,10 +1078,7 @@ def measure(args, rank, local_rank, world_size, dev, coll):
     if value_is_resident:
         value = resident_value
         value_leg = "resident"
-    spec_mode, spec_n, gen_n = world.specialization_status()
-    spec_info = {"mode": ("off", "cached", "compile")[spec_mode], "step_launches_specialized": spec_n, "step_launches_generic": gen_n,
-                 "what": "specialised code objects of the step kernel (raisimlib_amd/csrc/step_spec.h): the SAME kernel class compiled with the model's dimensions and the world's "
-                         "switches as compile-time constants; results bit-identical to the ahead-of-time class (tests/test_gpu_spec.py); counts are this world's launches of all legs"}
+    spec_info = spec_block()
     iters = world.get_solver_iterations()
     counts, _ = world.get_contacts()
     q_end, _ = world.get_state()
@@ -1121,13 +1199,9 @@ def measure(args, rank, local_rank, world_size, dev, coll):
                            "leg": primary_name, "gathered_rows_of_this_rank_correct": primary_leg.get("gathered_rows_of_this_rank_correct"),
                            "gathered_rows_correct_on_all_ranks": primary_leg.get("gathered_rows_correct_on_all_ranks"), "what": "round 5's `value`: one launch per control step, consecutive launches overlapping on the device (rsb_set_step_pipelining)"}
                           if res_leg is not None else None),
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": args.full,
             "config": {
-                "workload": recipe.name + ", dt=0.0025, 4 sub-steps per control step fused in one launch"
-                            + (", non-foot contact -> reset (rsg_anymal rule)" if reset else ", no resets")
-                            + (", EARLY TERMINATION at the sub-step of the first non-foot contact (not upstream's rule)" if args.early_termination else "")
-                            + ", obs (q,u,foot force) written each control step"
-                            + f"; stationary regime: {args.preroll} untimed pre-roll control steps before --warmup",
+                "workload": workload_text,
                 # the workload definitions behind the metric strings changed in round 3 (config 3: bases spread over +-6 m of the map instead
                 # of its centre; config 5: the STANDING regime is the default, rounds 1-2 measured what is now --atlas-regime collapsing):
                 # lines are comparable only at equal workload_version (and regime_name for config 5)
@@ -1135,7 +1209,7 @@ def measure(args, rank, local_rank, world_size, dev, coll):
                 "preroll_control_steps": args.preroll,
                 "regime": {"resets_per_control_step_mean": float(np.mean(resets)) if resets else None,
                            "env_age_control_steps_p10_p50_p90_p99": age_pct,
-                           "sampled_over_control_steps": SAMPLE_LAUNCHES},
+                           "sampled_over_control_steps": sampled},
                 "envs_per_gpu": N, "substeps_per_step": workload.SUBSTEPS,
                 "contact_solver": {"max_iter": args.max_iter or 150, "threshold_rel": 1e-5, "alpha": [1.0, 1.0, 1.0],
                                    "sweep": "grouped (block Jacobi across limbs, Gauss-Seidel within a limb)",
@@ -1167,14 +1241,52 @@ def measure(args, rank, local_rank, world_size, dev, coll):
             "state_at_end": {"solver_iters_mean": float(iters.mean()), "solver_iters_max": int(iters.max()),
                              "contacts_per_env": float(counts.mean()), "base_height_mean": float(q_end[:, 2].mean())},
         }
-        if world_size == 1 and not args.no_cpu:
+        if world_size == 1 and not args.no_cpu and args.full:
             # the CPU leg runs AFTER every GPU leg of the run (main): 16 busy threads exhaust the box's CPU quota, and a throttled host thread
             # cannot feed a 2 ms timed region (measured: the secondary configurations lost up to 30 % at --steps 20 behind a CPU leg)
             cpu_seconds, max_iter, nsc = args.cpu_seconds, args.max_iter, not args.no_self_collision
             gcf = gc0.astype(np.float32).astype(np.float64)
             out["_cpu_leg"] = lambda: cpu_baseline(recipe, max_iter, reset, cpu_seconds, q_start, u_start, gcf, gv0, step_start, self_collision=nsc)
+        if args.dump_outputs:       # the leg `value` reports, right after its timed brackets
+            out["outputs"] = dump_outputs(args.dump_outputs, snap["resident" if value_is_resident else legs["use"]])
     world.close()
     return out
+
+
+DUMP_BYTES_MAX = 64 << 20          # --dump-outputs: at most this many bytes in all; above it, the same seeded sample of envs from every array
+DUMP_SEED = 20240229
+
+
+def last_step_outputs(world, obs, done):
+    """What a caller of the timed leg receives from its last control step, as host float32 arrays of one row per env: the observation block
+    (device buffer `obs`, None where the exchange keeps no local block), the termination flags (device buffer `done`, None without resets) and the
+    state the world holds after the step."""
+    import torch
+    world.get_stream()                  # (joins a pipelined step before torch reads the buffers it writes)
+    torch.cuda.synchronize()
+    gc, gv = world.get_state()
+    out = {"gc": gc, "gv": gv}
+    if obs is not None:
+        out["obs"] = obs.float().cpu().numpy()
+    if done is not None:
+        out["done"] = done.cpu().numpy().astype(np.float32)
+    return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in out.items()}
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array (rows = envs).  Above DUMP_BYTES_MAX the same seeded sample of rows is kept from every array
+    and its env indices are written beside them (env_index.npy).  Returns {name: shape} as written."""
+    os.makedirs(dirname, exist_ok=True)
+    n = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(a.nbytes // max(a.shape[0], 1) for a in arrays.values())
+    if n * row_bytes > DUMP_BYTES_MAX:
+        keep = max(1, DUMP_BYTES_MAX // (row_bytes + 8))
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=keep, replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["env_index"] = idx.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), v)
+    return {k: list(v.shape) for k, v in arrays.items()}
 
 
 def finish_cpu_leg(o):
@@ -1185,6 +1297,8 @@ def finish_cpu_leg(o):
 
 def main():
     args = parse()
+    if args.repeats is None:       # (a plain run times exactly --steps steps; the diagnostic --closed-loop-only keeps its seven brackets per leg)
+        args.repeats = 7 if args.full or args.closed_loop_only else 1
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # started without a launcher: this process becomes the launcher of --gpus ranks (one per GPU)
         sys.exit(spawn_ranks(args))
@@ -1197,7 +1311,10 @@ def main():
         sys.exit(dry_run_ranks(args, rank, world_size))
     os.environ.setdefault("RSB_SPECIALIZE", {"compile": "compile", "cached": "1", "off": "0"}[args.specialization])   # every world of this process (the library reads it at rsb_create)
     os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")   # kernel arguments in device memory (this image's default; see rsb_world.hip)
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")       # the closed loop runs three streams that must overlap (two step streams + the action stage's) beside the caller's: HIP's default of 4 hardware queues aliases them
+    # the closed loop runs three streams that must overlap (two step streams + the action stage's) beside the caller's: HIP's default of 4 hardware queues
+    # can alias them (action-stage waits then time out, pipeline fault code 6), also where the environment names that default explicitly
+    if int(os.environ.get("GPU_MAX_HW_QUEUES") or 0) < 8:
+        os.environ["GPU_MAX_HW_QUEUES"] = "8"
     import torch
     import torch.distributed as dist
 
@@ -1223,7 +1340,7 @@ def main():
         print(json.dumps({"closed_loop": closed_loop_leg(args, dev, args.envs_per_gpu)}), flush=True)
         return
     out = measure(args, rank, local_rank, world_size, dev, coll)
-    default_run = (world_size == 1 and args.config == 2 and not args.no_secondary and not args.no_cpu and args.envs_per_gpu == ENVS_PER_GPU
+    default_run = (args.full and world_size == 1 and args.config == 2 and not args.no_secondary and not args.no_cpu and args.envs_per_gpu == ENVS_PER_GPU
                    and not (args.early_termination or args.no_reset or args.max_iter or args.lanes_per_env or args.no_self_collision or args.force_collective or args.lockstep))
     if rank == 0 and default_run:
         # what the driver's default run also records: the other single-GPU configurations of BASELINE.json with
@@ -1234,6 +1351,7 @@ def main():
         for cfg in (3, 5):          # the GPU legs first, ...
             a2 = copy.copy(args)
             a2.config, a2.cpu_seconds = cfg, min(args.cpu_seconds, 7.0)
+            a2.dump_outputs = None      # (DIR holds the headline's outputs only)
             try:
                 second[cfg] = measure(a2, rank, local_rank, world_size, dev, coll)
             except Exception as e:      # a secondary line must never take the headline down

@@ -7,6 +7,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+# The library asks for 8 hardware queues when it loads (raisimlib_amd/csrc/rsb_world.hip) but keeps a value the environment already names; the
+# closed-loop pipeline's three overlapping streams beside the caller's can alias on HIP's default of 4.  Set before any test starts HIP, so that the
+# suite and the programs it starts (bench.py, tests/cpp) run as the library expects; a test that wants fewer queues passes its own value.
+if int(os.environ.get("GPU_MAX_HW_QUEUES") or 0) < 8:
+    os.environ["GPU_MAX_HW_QUEUES"] = "8"
+
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu via gpurun)")

@@ -12,9 +12,9 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("config", [2, 3, 5])
-def test_bench_prints_the_contract_line(built_lib, config):
+def test_bench_prints_the_contract_line(built_lib, config, tmp_path):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--preroll", "8",
-           "--config", str(config), "--cpu-seconds", "2"]
+           "--config", str(config), "--cpu-seconds", "2", "--full", "--dump-outputs", str(tmp_path / "out")]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=280, cwd="/tmp")
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1]
@@ -75,12 +75,54 @@ def test_bench_prints_the_contract_line(built_lib, config):
         assert len(tp["attempts_env_steps_per_s"]) == 3 and sorted(tp["attempts_env_steps_per_s"])[1] == tp["env_steps_per_s"]      # the median of three attempts
     else:
         assert "secondary" not in b
+    # --dump-outputs holds the headline configuration's arrays only (the secondary configurations of the config-2 line write none), as the line reports them
+    import numpy as np
+    files = {k: list(np.load(tmp_path / "out" / f"{k}.npy").shape) for k in ("obs", "done", "gc", "gv")}
+    assert b["outputs"] == files and sorted(os.listdir(tmp_path / "out")) == ["done.npy", "gc.npy", "gv.npy", "obs.npy"]
+    assert files["obs"][1] > files["gc"][1] + files["gv"][1] and files["done"] == [4096]
+    if config == 2:
+        assert files == {"obs": [4096, 49], "done": [4096], "gc": [4096, 19], "gv": [4096, 18]}
+
+
+def test_bench_plain_run_times_exactly_its_steps_and_dumps_its_outputs(built_lib, tmp_path):
+    """A plain run (no --full): ONE bracket of exactly --steps control steps of the leg `value` reports (the resident one), the line's headline fields
+    and nothing measured by runs of their own; --dump-outputs writes that leg's last control step, and two runs with the same arguments write the
+    same arrays"""
+    import numpy as np
+    got = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "40", "--warmup", "5", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=280, cwd="/tmp")
+        assert r.returncode == 0, r.stderr[-2000:]
+        b = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])
+        assert b["full"] is False and b["n_gpus"] == 1 and b["steps"] == 40 and b["warmup"] == 5 and b["repeats"] == 1
+        assert b["unit"] == "env-steps/s" and b["higher_is_better"] is True and b["dtype"] == "f32" and b["value"] > 1e6
+        assert b["metric"].startswith("env-steps/sec") and b["value_leg"] == "resident" and b["resident_leg_error"] is None
+        assert abs(b["value"] - 4096 * 4 * 40 / (b["ms_per_step"] * 40 * 1e-3)) < 1e-6 * b["value"]
+        for k in ("roofline", "cpu_baseline", "lockstep", "pipelined", "resident", "secondary", "closed_loop", "boundary_template_path"):
+            assert k not in b, k
+        assert b["specialization"]["step_launches_generic"] == 0
+        assert b["outputs"] == {"gc": [4096, 19], "gv": [4096, 18], "obs": [4096, 49], "done": [4096]}
+        arrays = {k: np.load(d / f"{k}.npy") for k in b["outputs"]}
+        for k, v in arrays.items():
+            assert v.dtype == np.float32 and np.isfinite(v).all(), k
+        assert set(np.unique(arrays["done"])) <= {0.0, 1.0}
+        # the obs block is gathered after the last control step's integration, before terminated envs are reset: where no env was reset, its
+        # (q, u) columns are the state the world holds after that step
+        live = arrays["done"] == 0
+        assert live.sum() > 2048
+        assert np.allclose(arrays["obs"][live, :19], arrays["gc"][live], rtol=0, atol=1e-6)
+        assert np.allclose(arrays["obs"][live, 19:37], arrays["gv"][live], rtol=0, atol=1e-6)
+        got.append(arrays)
+    for k in got[0]:
+        assert np.array_equal(got[0][k], got[1][k]), k
 
 
 def test_bench_collective_path_on_one_rank(built_lib):
     """the obs all-gather (RCCL) of the N>1 step, forced onto a one-rank group: the same code path `--gpus N` runs per rank"""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--preroll", "8",
-           "--force-collective", "--no-cpu"]
+           "--force-collective", "--no-cpu", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=280, cwd="/tmp")
     assert r.returncode == 0, r.stderr[-2000:]
     b = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])
@@ -94,7 +136,7 @@ def test_bench_collective_path_on_one_rank(built_lib):
 def test_bench_lockstep_flag(built_lib):
     """`--lockstep`: no pipelining anywhere, the all-gather in line on the launch stream (the line of rounds 1-3)"""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--preroll", "8",
-           "--force-collective", "--no-cpu", "--lockstep"]
+           "--force-collective", "--no-cpu", "--lockstep", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=280, cwd="/tmp")
     assert r.returncode == 0, r.stderr[-2000:]
     b = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])
@@ -118,7 +160,7 @@ def test_bench_two_leg_order_of_an_n_gpu_run_on_one_rank(built_lib):
     and the ranks' devices with them - forced onto a one-rank group (RSB_BENCH_TWO_LEGS=1 --force-collective): the only way this code path meets a
     GPU before the driver's scaling run.  And the default single-GPU line's closed_loop block and roofline fractions."""
     env = dict(os.environ, RSB_BENCH_TWO_LEGS="1")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--preroll", "8", "--force-collective", "--no-cpu"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--preroll", "8", "--force-collective", "--no-cpu", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=280, cwd="/tmp", env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     b = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])
@@ -158,7 +200,7 @@ def test_bench_two_real_ranks_on_one_device(built_lib):
     resident leg (one gather of the launch's [steps, N, obs] block) with real kernels and real ranks.  Every leg's gathered block holds this rank's own rows
     in its slice, on BOTH ranks; the two ranks' shards differ (per-env seeds by global index)."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-device", "--backend", "gloo", "--steps", "6", "--warmup", "2", "--preroll", "8",
-           "--no-cpu", "--envs-per-gpu", "1024"]
+           "--no-cpu", "--envs-per-gpu", "1024", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400, cwd="/tmp")
     assert r.returncode == 0, r.stderr[-3000:]
     b = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])

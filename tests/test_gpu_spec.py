@@ -131,7 +131,7 @@ def test_the_manifest_covers_the_workloads_of_bench_py(built_lib, tmp_path):
     rec = tmp_path / "missing.txt"
     env = dict(os.environ, RSB_SPEC_RECORD=str(rec))
     env.pop("RSB_SPECIALIZE", None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--specialization", "cached", "--steps", "4", "--warmup", "2", "--no-cpu", "--repeats", "3"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--specialization", "cached", "--steps", "4", "--warmup", "2", "--no-cpu", "--repeats", "3", "--full"],
                        env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     b = json.loads([l for l in p.stdout.strip().splitlines() if l.startswith("{")][-1])

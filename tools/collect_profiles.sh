@@ -7,15 +7,15 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py 2>/dev/null | tail -1 > $O/bench_default.json
-python $R/bench.py --max-iter 30 --no-cpu 2>/dev/null | tail -1 > $O/bench_maxiter30.json
-python $R/bench.py --no-reset --no-cpu 2>/dev/null | tail -1 > $O/bench_noreset.json
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o bench -- python $R/bench.py --no-cpu > $O/trace_bench.log 2>&1
+python $R/bench.py --full 2>/dev/null | tail -1 > $O/bench_default.json
+python $R/bench.py --full --max-iter 30 --no-cpu 2>/dev/null | tail -1 > $O/bench_maxiter30.json
+python $R/bench.py --full --no-reset --no-cpu 2>/dev/null | tail -1 > $O/bench_noreset.json
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o bench -- python $R/bench.py --full --no-cpu > $O/trace_bench.log 2>&1
 # PMC passes: counters only, one group per pass (never combined with trace domains)
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o run -- python $R/bench.py --no-cpu --steps 50 --warmup 50 > /dev/null 2>&1
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o run -- python $R/bench.py --no-cpu --steps 50 --warmup 50 > /dev/null 2>&1
-rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS --output-format csv -d $O/pmc_sq -o run -- python $R/bench.py --no-cpu --steps 50 --warmup 50 > /dev/null 2>&1
-rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_VMEM GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_sq2 -o run -- python $R/bench.py --no-cpu --steps 50 --warmup 50 > /dev/null 2>&1
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o run -- python $R/bench.py --full --no-cpu --steps 50 --warmup 50 > /dev/null 2>&1
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o run -- python $R/bench.py --full --no-cpu --steps 50 --warmup 50 > /dev/null 2>&1
+rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS --output-format csv -d $O/pmc_sq -o run -- python $R/bench.py --full --no-cpu --steps 50 --warmup 50 > /dev/null 2>&1
+rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_VMEM GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_sq2 -o run -- python $R/bench.py --full --no-cpu --steps 50 --warmup 50 > /dev/null 2>&1
 python - <<PY > $O/pmc_summary.txt
 import csv, glob, collections, json
 out = {}

@@ -27,7 +27,7 @@ for step in "$@"; do
   case "$kind" in
     pytest) ( timeout $T python -m pytest $arg -q -x --timeout 600 --durations=6 ) > "$O/${n}_${label:-pytest}.log" 2>&1; echo "rc=$?" >> "$O/${n}_${label:-pytest}.log"; tail -6 "$O/${n}_${label:-pytest}.log" ;;
     smoke)  timeout $T python -c "import __graft_entry__ as g; g.smoke()" > "$O/${n}_${label:-smoke}.log" 2>&1; echo "rc=$?" >> "$O/${n}_${label:-smoke}.log"; tail -2 "$O/${n}_${label:-smoke}.log" ;;
-    bench)  timeout $T python bench.py $arg 2> "$O/${n}_${label:-bench}.log" | tail -1 > "$O/${n}_${label:-bench}.json"; echo "rc=${PIPESTATUS[0]} args: $arg" >> "$O/${n}_${label:-bench}.log"
+    bench)  timeout $T python bench.py --full $arg 2> "$O/${n}_${label:-bench}.log" | tail -1 > "$O/${n}_${label:-bench}.json"; echo "rc=${PIPESTATUS[0]} args: $arg" >> "$O/${n}_${label:-bench}.log"
             python - "$O/${n}_${label:-bench}.json" <<'PY'
 import json, sys
 try:
@@ -41,15 +41,15 @@ except Exception as e:
     print("bench: no JSON line (", e, ")")
 PY
             ;;
-    trace)  ( cd /tmp && timeout $T rocprofv3 --kernel-trace --stats --output-format csv -d "$O/${n}_${label:-trace}" -o run -- python "$R/bench.py" $arg ) > "$O/${n}_${label:-trace}.log" 2>&1; echo "rc=$?" >> "$O/${n}_${label:-trace}.log" ;;
+    trace)  ( cd /tmp && timeout $T rocprofv3 --kernel-trace --stats --output-format csv -d "$O/${n}_${label:-trace}" -o run -- python "$R/bench.py" --full $arg ) > "$O/${n}_${label:-trace}.log" 2>&1; echo "rc=$?" >> "$O/${n}_${label:-trace}.log" ;;
     pmc)    ctr=${arg%%:*}; barg=${arg#*:}
-            ( cd /tmp && timeout $T rocprofv3 --pmc $ctr --output-format csv -d "$O/${n}_${label:-pmc}" -o run -- python "$R/bench.py" $barg ) > "$O/${n}_${label:-pmc}.log" 2>&1; echo "rc=$? counters: $ctr" >> "$O/${n}_${label:-pmc}.log" ;;
+            ( cd /tmp && timeout $T rocprofv3 --pmc $ctr --output-format csv -d "$O/${n}_${label:-pmc}" -o run -- python "$R/bench.py" --full $barg ) > "$O/${n}_${label:-pmc}.log" 2>&1; echo "rc=$? counters: $ctr" >> "$O/${n}_${label:-pmc}.log" ;;
     py)     timeout $T python $arg > "$O/${n}_${label:-py}.log" 2>&1; echo "rc=$?" >> "$O/${n}_${label:-py}.log"; tail -5 "$O/${n}_${label:-py}.log" ;;
     sh)     timeout $T bash -c "$arg" > "$O/${n}_${label:-sh}.log" 2>&1; echo "rc=$?" >> "$O/${n}_${label:-sh}.log"; tail -5 "$O/${n}_${label:-sh}.log" ;;
     ab)     reps=${arg%%:*}; rest=${arg#*:}; libs=${rest%%:*}; barg=${rest#*:}
             : > "$O/${n}_${label:-ab}.txt"
             for r in $(seq 1 $reps); do for lib in ${libs//,/ }; do
-              v=$(RSB_LIB_PATH=$R/raisimlib_amd/lib/$lib timeout $T python bench.py $barg 2>/dev/null | tail -1 | python -c "import json,sys; d=json.load(sys.stdin); print(round(d['value']), round((d.get('lockstep') or {}).get('value') or 0))" 2>/dev/null)
+              v=$(RSB_LIB_PATH=$R/raisimlib_amd/lib/$lib timeout $T python bench.py --full $barg 2>/dev/null | tail -1 | python -c "import json,sys; d=json.load(sys.stdin); print(round(d['value']), round((d.get('lockstep') or {}).get('value') or 0))" 2>/dev/null)
               echo "$lib $v" >> "$O/${n}_${label:-ab}.txt"
             done; done; cat "$O/${n}_${label:-ab}.txt" ;;
     *)      echo "lease.sh: unknown step kind '$kind'" ;;
