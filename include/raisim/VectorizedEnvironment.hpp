@@ -46,6 +46,10 @@ struct VecEnvConfig {
   std::vector<std::string> foot_collision_suffixes = {"_foot"};
   int device = 0;
   bool early_termination = false;         // rsb_set_early_termination: not upstream's rule, see include/rsb.h
+  // running observation statistics on the device (rsb_env_observe_normalized & co.): upstream's VectorizedEnvironment normalises by default
+  // (normalizeObservation = true); here the default is OFF so that existing callers keep their raw observations
+  bool normalize_observation = false;
+  double obs_clip = 0.0;                  // with normalize_observation: clamp normalised observations (observe and rolloutMlp's input) to +-obs_clip; 0: none, as the template path
 };
 
 class DeviceVectorizedEnvironment {
@@ -85,13 +89,30 @@ class DeviceVectorizedEnvironment {
 
   void reset() { RSB_CHECK(rsb_env_reset(world_.handle())); }
 
-  /// ob: float [num_envs, obDim] row-major, written in place (updateStatistics is accepted for source compatibility)
-  void observe(float* ob, int rows, int cols, bool /*updateStatistics*/ = false) {
+  /// ob: float [num_envs, obDim] row-major, written in place.  With cfg.normalize_observation the observation is normalised with the running
+  /// statistics on the device, after merging this batch into them when updateStatistics (upstream's semantics); otherwise it is raw and the flag is ignored
+  void observe(float* ob, int rows, int cols, bool updateStatistics = false) {
     RSFATAL_IF(rows != n_ || cols != obDim_, "observe: buffer must be [num_envs, obDim]");
-    RSB_CHECK(rsb_env_observe(world_.handle(), ob, RSB_HOST));
+    if (cfg_.normalize_observation) RSB_CHECK(rsb_env_observe_normalized(world_.handle(), ob, updateStatistics ? 1 : 0, (float)cfg_.obs_clip, RSB_HOST));
+    else RSB_CHECK(rsb_env_observe(world_.handle(), ob, RSB_HOST));
   }
-  /// the same with a device buffer (e.g. a torch CUDA tensor's data_ptr): nothing crosses PCIe, nothing synchronises
+  /// the same with a device buffer (e.g. a torch CUDA tensor's data_ptr): nothing crosses PCIe, nothing synchronises.  Always the raw observation.
   void observeDevice(float* ob_device) { RSB_CHECK(rsb_env_observe(world_.handle(), ob_device, RSB_DEVICE)); }
+  /// device buffer, honouring cfg.normalize_observation as observe() does (statistics stay on the device, nothing synchronises)
+  void observeDevice(float* ob_device, bool updateStatistics) {
+    if (cfg_.normalize_observation) RSB_CHECK(rsb_env_observe_normalized(world_.handle(), ob_device, updateStatistics ? 1 : 0, (float)cfg_.obs_clip, RSB_DEVICE));
+    else RSB_CHECK(rsb_env_observe(world_.handle(), ob_device, RSB_DEVICE));
+  }
+  /// the running observation statistics (the template path's signatures; host arrays [obDim]; synchronise).  count is kept in double on the device.
+  void getObStatistics(float* mean, float* var, float& count) {
+    double c = 0.0;
+    RSB_CHECK(rsb_env_get_obs_stats(world_.handle(), mean, var, &c));
+    count = (float)c;
+  }
+  void setObStatistics(const float* mean, const float* var, float count) { RSB_CHECK(rsb_env_set_obs_stats(world_.handle(), mean, var, (double)count)); }
+  /// merges recorded RAW observations into the statistics, batch after batch: a closed-loop rollout's ob [batches, num_envs, obDim] (device memory;
+  /// e.g. K + 1 batches after a rollout of K steps).  Nothing synchronises.
+  void updateObStatistics(const float* rolloutObDevice, int batches) { RSB_CHECK(rsb_env_obs_stats_update(world_.handle(), rolloutObDevice, batches, 0, RSB_DEVICE)); }
 
   /// action: float [num_envs, actionDim]; reward: float [num_envs]; done: bool [num_envs] — all written in place
   void step(const float* action, int rows, int cols, float* reward, bool* done) {
@@ -162,6 +183,10 @@ class DeviceVectorizedEnvironment {
       }
     }
     mlp_.activation = activation; mlp_.leaky_slope = 0.01f; mlp_.clip = clip;
+    if (cfg_.normalize_observation) {     // the network sees the observation normalised with the LIVE statistics as of this run's launch
+      RSB_CHECK(rsb_env_obs_stats_device(world_.handle(), &mlp_.ob_mean, &mlp_.ob_inv_std));
+      mlp_.ob_clip = (float)cfg_.obs_clip;
+    }
     RSB_CHECK(rsb_closed_loop_run_mlp(world_.handle(), steps, &mlp_));
   }
   /// waits for everything in flight; RSB_OK, or RSB_E_PIPELINE once after a pipeline fault (the steps were then replayed in lock-step: results are valid)

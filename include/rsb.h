@@ -29,6 +29,9 @@
  *                                       <- ArticulatedSystem::getMassMatrix()/getNonlinearities()
  *   rsb_gather_obs                      <- (new) the (q, u, contact-force) observation block that
  *                                          VectorizedEnvironment::observe() is built from
+ *   rsb_env_observe_normalized / rsb_env_get_obs_stats / rsb_env_set_obs_stats
+ *                                       <- VectorizedEnvironment::observe(ob, updateStatistics),
+ *                                          getObStatistics/setObStatistics (raisimGymTorch, absent)
  *
  * Conventions
  *   - No exceptions cross this ABI. Every call returns RSB_OK (0) or a negative rsb_status;
@@ -371,6 +374,28 @@ int rsb_env_observe(rsb_world* w, float* ob, int space);           /* [N, ob_dim
  * starts from, i.e. after the resets) out, any of which may be NULL; all in `space`.  Two launches: the step kernel
  * (action -> PD targets in its prologue) and one reward / termination / reset / observation kernel. */
 int rsb_env_step(rsb_world* w, const float* action, float* reward, uint8_t* done, float* ob_next, int space);
+
+/* Running observation statistics of the env task, on the device (the template path's updateObservationStatisticsAndNormalize
+ * [RECALL raisimGymTorch VectorizedEnvironment::observe(ob, updateStatistics), getObStatistics, setObStatistics]).  Per world, from the
+ * first rsb_env_configure on: count = 1e-4, mean = 0, var = 1 (ob_dim entries each; kept in fp64, count included).  A batch of N
+ * observations is merged with its mean and population variance over the N envs (Chan's formula, upstream's arithmetic); an observation
+ * is normalised as clamp((ob - mean) * inv_std, -clip, clip) with inv_std = 1 / sqrt(var + 1e-8) rounded to float once, clip <= 0: none.
+ * Every call is enqueued on the world's stream (ordered with steps, pipelined or resident, and closed-loop runs); the RSB_DEVICE forms
+ * do not synchronise.  Each world (each rank) keeps its own statistics.  rsb_env_observe, rsb_env_step's ob_next and the closed-loop
+ * runs stay raw.
+ *   rsb_env_observe_normalized  rsb_env_observe, then (update_statistics != 0) the batch merged into the statistics, then normalised.
+ *   rsb_env_obs_stats_update    n_batches batches of [N, ob_dim] floats, batch_stride floats apart (0: N * ob_dim), merged in order - a
+ *                               closed-loop rollout's ob [K + 1, N, ob_dim]; one call over B batches = B calls over one batch, bit for bit.
+ *   rsb_env_obs_normalize       rows x ob_dim floats normalised with the current statistics (in == out allowed): a stored rollout.
+ *   rsb_env_get_obs_stats / rsb_env_set_obs_stats   host arrays [ob_dim] (any output may be NULL); synchronise.
+ *   rsb_env_obs_stats_device    device pointers mean [ob_dim] and inv_std [ob_dim] (float), valid for the world's lifetime and updated in
+ *                               stream order: an rsb_mlp_policy's ob_mean / ob_inv_std, read by each run as of its launch. */
+int rsb_env_observe_normalized(rsb_world* w, float* ob, int update_statistics, float clip, int space);
+int rsb_env_obs_stats_update(rsb_world* w, const float* obs, int n_batches, long long batch_stride, int space);
+int rsb_env_obs_normalize(rsb_world* w, const float* in, float* out, long long rows, float clip, int space);
+int rsb_env_get_obs_stats(rsb_world* w, float* mean, float* var, double* count);
+int rsb_env_set_obs_stats(rsb_world* w, const float* mean, const float* var, double count);
+int rsb_env_obs_stats_device(rsb_world* w, const float** mean, const float** inv_std);
 
 /* zero-copy access to the resident state (device pointers; row-major [N,dim] float32): see rsb_field */
 void* rsb_device_ptr(rsb_world* w, int field);

@@ -197,6 +197,12 @@ PROTOTYPES = {
     "rsb_env_reset": (_I, [_VP]),
     "rsb_env_observe": (_I, [_VP, _FP, _I]),
     "rsb_env_step": (_I, [_VP, _FP, _FP, _FP, _FP, _I]),
+    "rsb_env_observe_normalized": (_I, [_VP, _FP, _I, C.c_float, _I]),
+    "rsb_env_obs_stats_update": (_I, [_VP, _FP, _I, C.c_longlong, _I]),
+    "rsb_env_obs_normalize": (_I, [_VP, _FP, _FP, C.c_longlong, C.c_float, _I]),
+    "rsb_env_get_obs_stats": (_I, [_VP, _FP, _FP, C.POINTER(_D)]),
+    "rsb_env_set_obs_stats": (_I, [_VP, _FP, _FP, _D]),
+    "rsb_env_obs_stats_device": (_I, [_VP, C.POINTER(_VP), C.POINTER(_VP)]),
     "rsb_device_ptr": (_VP, [_VP, _I]),
     "rsb_last_kernel_ms": (_I, [_VP, C.POINTER(C.c_float)]),
     "rsb_enable_timing": (_I, [_VP, _I]),

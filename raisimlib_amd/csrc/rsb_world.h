@@ -124,6 +124,10 @@ struct rsb_world {
   unsigned long long env_allowed = 0;
   float *d_env_mean = nullptr, *d_env_gc0 = nullptr, *d_env_gv0 = nullptr, *d_env_io = nullptr, *d_env_ob = nullptr, *d_env_reward = nullptr, *d_env_tau2 = nullptr;
   uint8_t* d_env_done = nullptr;
+  // running observation statistics of the env task (rsb_obstats.hip): [mean D | var D | count] fp64, the float views [mean D | inv_std D] the
+  // normaliser and an MLP stage read, and the fold's scratch: block partials and batch moments (obs_part_batches batches of them)
+  double* d_obs_stats = nullptr; float* d_obs_view = nullptr; double* d_obs_part = nullptr;
+  int obs_part_batches = 0;
   std::vector<hipEvent_t> ring0, ring1;   // event pairs around the most recent step-kernel launches (rsb_enable_timing(w, n))
   size_t ring_next = 0, ring_count = 0;
   int timing_stride = 1;       // events bracket every timing_stride-th launch only (an event pair costs ~7 us of stream time)
@@ -196,6 +200,8 @@ int launch_env_obs(rsb_world* w, float* dst, hipStream_t s);
 int launch_dynamics_query(rsb_world* w, hipStream_t s);           // M, h and M^-1 of the current state into d_M / d_h / d_Minv (the query kernels)
 int resident_class(rsb_world* w, int stage, int mlp_width);          // the resident kernel class (CL bits) of this world as configured, or -1 with the reason in the error string
 int rk4_integrate(rsb_world* w, int nsub);                        // rsb_rk4.hip     // the stand-alone env-task observation of the current state
+int obs_stats_init(rsb_world* w);                                 // rsb_obstats.hip: the observation statistics at their initial state (rsb_env_configure, once)
+void obs_stats_free(rsb_world* w);                                // rsb_obstats.hip (rsb_destroy)
 // rsb_pipeline.hip
 hipStream_t stream_of(rsb_world* w);                              // the world's stream for any use other than a pipelined launch (joins first)
 int pipe_join(rsb_world* w);

@@ -800,6 +800,7 @@ int rsb_destroy(rsb_world* w) {
   if (w->d_rk) (void)hipFree(w->d_rk);
   if (w->d_env_act) (void)hipFree(w->d_env_act);
   if (w->d_env_gc0_rows) { (void)hipFree(w->d_env_gc0_rows); (void)hipFree(w->d_env_gv0_rows); }
+  obs_stats_free(w);
   if (w->own_stream && w->stream) (void)hipStreamDestroy(w->stream);
   delete w;
   return RSB_OK;
@@ -1592,7 +1593,7 @@ int rsb_env_configure(rsb_world* w, const rsb_env_config* cfg, const float* acti
   HIP_TRY(hipMemcpyAsync(w->d_env_gv0, gv_init, nv * sizeof(float), hipMemcpyHostToDevice, stream_of(w)));
   HIP_TRY(hipStreamSynchronize(stream_of(w)));
   w->env_cfg = *cfg; w->env_allowed = allowed; w->env_ready = true;
-  return RSB_OK;
+  return obs_stats_init(w);      // (once per world: a later call - a new control_dt, say - keeps the statistics)
 }
 int rsb_env_set_reset_states(rsb_world* w, const float* gc0, const float* gv0, int space) {
   if (!w || ((gc0 != nullptr) != (gv0 != nullptr)) || (space != RSB_HOST && space != RSB_DEVICE)) { rsb::set_error("rsb_env_set_reset_states: bad argument"); return RSB_E_INVALID; }

@@ -124,7 +124,9 @@ PYBIND11_MODULE(RSG_MODULE_NAME, m) {
       .def_readwrite("torque_reward_coeff", &raisim::VecEnvConfig::torque_reward_coeff)
       .def_readwrite("terminal_reward", &raisim::VecEnvConfig::terminal_reward)
       .def_readwrite("gc_init", &raisim::VecEnvConfig::gc_init)
-      .def_readwrite("device", &raisim::VecEnvConfig::device);
+      .def_readwrite("device", &raisim::VecEnvConfig::device)
+      .def_readwrite("normalize_observation", &raisim::VecEnvConfig::normalize_observation)    // (default False: upstream's is True)
+      .def_readwrite("obs_clip", &raisim::VecEnvConfig::obs_clip);
 
   using DevEnv = raisim::DeviceVectorizedEnvironment;
   py::class_<DevEnv>(m, "DeviceRaisimGymEnv")
@@ -139,10 +141,33 @@ PYBIND11_MODULE(RSG_MODULE_NAME, m) {
              e.step(action.data(), e.getNumOfEnvs(), e.getActionDim(), vec(reward, e.getNumOfEnvs(), "step: reward float32 [num_envs]"), done.mutable_data());
            }, py::arg("action").noconvert(), py::arg("reward").noconvert(), py::arg("done").noconvert())
       // device-resident loop: the arguments are DEVICE addresses (torch.Tensor.data_ptr()); nothing crosses PCIe, nothing synchronises
-      .def("observeDevice", [](DevEnv& e, std::uintptr_t ob) { e.observeDevice(reinterpret_cast<float*>(ob)); })
+      .def("observeDevice", [](DevEnv& e, std::uintptr_t ob, bool u) { e.observeDevice(reinterpret_cast<float*>(ob), u); }, py::arg("ob"), py::arg("updateStatistics") = false)
       .def("stepDevice", [](DevEnv& e, std::uintptr_t action, std::uintptr_t reward, std::uintptr_t done, std::uintptr_t ob_next) {
              e.stepDevice(reinterpret_cast<const float*>(action), reinterpret_cast<float*>(reward), reinterpret_cast<uint8_t*>(done), reinterpret_cast<float*>(ob_next));
            }, py::arg("action"), py::arg("reward"), py::arg("done"), py::arg("ob_next") = 0)
+      .def("updateObStatistics", [](DevEnv& e, std::uintptr_t ob, int batches) { e.updateObStatistics(reinterpret_cast<const float*>(ob), batches); },
+           py::arg("rolloutOb"), py::arg("batches"))
+      // the rest of the surface RaisimGymVecEnv calls (the same as RaisimGymEnv's)
+      .def("setSeed", &DevEnv::setSeed)
+      .def("close", &DevEnv::close)
+      .def("isTerminalState", [](DevEnv& e, BVec t) {
+             need(t.size() == e.getNumOfEnvs() && t.writeable(), "isTerminalState: bool [num_envs] array expected");
+             e.isTerminalState(t.mutable_data());
+           }, py::arg("terminalState").noconvert())
+      .def("setSimulationTimeStep", &DevEnv::setSimulationTimeStep)
+      .def("setControlTimeStep", &DevEnv::setControlTimeStep)
+      .def("turnOnVisualization", &DevEnv::turnOnVisualization)
+      .def("turnOffVisualization", &DevEnv::turnOffVisualization)
+      .def("curriculumUpdate", &DevEnv::curriculumUpdate)
+      .def("getObStatistics", [](DevEnv& e, FMat mean, FMat var) {
+             float count = 0.f;
+             e.getObStatistics(vec(mean, e.getObDim(), "getObStatistics: mean must be float32 [obDim]"), vec(var, e.getObDim(), "getObStatistics: var must be float32 [obDim]"), count);
+             return count;
+           }, py::arg("mean").noconvert(), py::arg("var").noconvert())
+      .def("setObStatistics", [](DevEnv& e, FMat mean, FMat var, float count) {
+             need(mean.size() == e.getObDim() && var.size() == e.getObDim(), "setObStatistics: float32 [obDim] arrays expected");
+             e.setObStatistics(mean.data(), var.data(), count);
+           })
       .def("getObDim", &DevEnv::getObDim)
       .def("getActionDim", &DevEnv::getActionDim)
       .def("getNumOfEnvs", &DevEnv::getNumOfEnvs);

@@ -87,17 +87,26 @@ class VecEnv:
     def reset(self):
         check(self.world.L.rsb_env_reset(self.world.handle), "rsb_env_reset")
 
-    def observe(self, out=None):
+    def observe(self, out=None, normalized=False, update_statistics=False, clip=0.0):
+        """The env-task observation [num_envs, num_obs].  normalized=True: normalised with the library's running statistics on the device
+        (rsb_env_observe_normalized; after merging this batch into them when update_statistics; clip > 0 clamps to +-clip); the default is
+        the raw observation."""
         w = self.world
+
+        def call(ptr, space):
+            if normalized:
+                check(w.L.rsb_env_observe_normalized(w.handle, ptr, int(bool(update_statistics)), float(clip), space), "rsb_env_observe_normalized")
+            else:
+                check(w.L.rsb_env_observe(w.handle, ptr, space), "rsb_env_observe")
         if out is not None and self._is_torch(out):
             import torch
             self._check_tensor(out, (self.num_envs, self.num_obs), torch.float32, "out")
-            check(w.L.rsb_env_observe(w.handle, C.c_void_p(out.data_ptr()), RSB_DEVICE), "rsb_env_observe")
+            call(C.c_void_p(out.data_ptr()), RSB_DEVICE)
             return out
         ob = np.zeros((self.num_envs, self.num_obs), np.float32) if out is None else out
         if not (isinstance(ob, np.ndarray) and ob.dtype == np.float32 and ob.flags.c_contiguous and ob.shape == (self.num_envs, self.num_obs)):
             raise ValueError("VecEnv.observe: out must be a C-contiguous float32 array [num_envs, num_obs]")
-        check(w.L.rsb_env_observe(w.handle, _hp(ob), RSB_HOST), "rsb_env_observe")
+        call(_hp(ob), RSB_HOST)
         return ob
 
     def step(self, action, reward=None, done=None, ob_next=None):
@@ -179,12 +188,13 @@ class VecEnv:
         check(w.L.rsb_closed_loop_run_linear(w.handle, K, C.byref(p)), "rsb_closed_loop_run_linear")
 
     def rollout_mlp(self, n_steps, layers, activation="leaky_relu", leaky_slope=0.01, ob_mean=None, ob_var=None, ob_clip=10.0, eps=1e-8,
-                    noise=None, clip=0.0, rollout=None):
+                    noise=None, clip=0.0, rollout=None, live_ob_stats=False):
         """n_steps control steps with the in-repo MLP stage in the loop (rsb_closed_loop_run_mlp): the actor of a raisimGymTorch-style PPO run.
         `layers`: [(weight [out, in], bias [out] or None), ...] torch CUDA tensors in torch.nn.Linear's layout (e.g. [(l.weight, l.bias) for l in
         actor if isinstance(l, torch.nn.Linear)]); hidden layers use `activation` ("tanh" | "relu" | "leaky_relu"), the last one is linear.
         ob_mean / ob_var [num_obs]: frozen running statistics, the network sees clamp((ob - mean) / sqrt(var + eps), +-ob_clip) (this class's
-        observe_normalized); None: the raw observation.  noise / clip / rollout as rollout_linear.  Nothing synchronises."""
+        observe_normalized); None: the raw observation.  live_ob_stats=True instead: the library's running statistics on the device
+        (obs_statistics), as they stand when the run is launched, with ob_clip.  noise / clip / rollout as rollout_linear.  Nothing synchronises."""
         import torch
         w = self.world
         K, N = int(n_steps), self.num_envs
@@ -211,7 +221,12 @@ class VecEnv:
             p.dims[i] = d
         p.activation = {"tanh": 0, "relu": 1, "leaky_relu": 2}[activation]
         p.leaky_slope = float(leaky_slope)
-        if ob_mean is not None:
+        if live_ob_stats:
+            if ob_mean is not None or ob_var is not None:
+                raise ValueError("rollout_mlp: live_ob_stats and ob_mean / ob_var exclude each other")
+            p.ob_mean, p.ob_inv_std = self.obs_statistics_device()
+            p.ob_clip = float(ob_clip)
+        elif ob_mean is not None:
             self._check_tensor(ob_mean, (self.num_obs,), torch.float32, "ob_mean")
             self._check_tensor(ob_var, (self.num_obs,), torch.float32, "ob_var")
             inv = torch.rsqrt(ob_var + eps).contiguous()
@@ -230,7 +245,66 @@ class VecEnv:
         self._keep = (keep, noise, rollout)          # the launches are asynchronous: keep the tensors alive until the next call
         check(w.L.rsb_closed_loop_run_mlp(w.handle, K, C.byref(p)), "rsb_closed_loop_run_mlp")
 
-    # -- running observation statistics (RaisimGymVecEnv's normalize_ob / RunningMeanStd [RECALL]) -------------------
+    # -- running observation statistics kept by the library on the device (rsb_env_observe_normalized & co.; include/rsb.h) ----------
+    def update_obs_statistics(self, ob):
+        """Merges recorded RAW observations into the library's statistics, batch after batch in order: ob [B, num_envs, num_obs] (e.g. a
+        closed-loop rollout's ob) or [num_envs, num_obs]; a torch CUDA tensor (nothing synchronises) or a numpy array."""
+        w = self.world
+        shape = tuple(ob.shape)
+        if len(shape) not in (2, 3) or shape[-2:] != (self.num_envs, self.num_obs):
+            raise ValueError(f"update_obs_statistics: ob must be [B, {self.num_envs}, {self.num_obs}] or [{self.num_envs}, {self.num_obs}], got {shape}")
+        nb = 1 if len(shape) == 2 else shape[0]
+        if self._is_torch(ob):
+            import torch
+            self._check_tensor(ob, shape, torch.float32, "ob")
+            check(w.L.rsb_env_obs_stats_update(w.handle, C.c_void_p(ob.data_ptr()), nb, 0, RSB_DEVICE), "rsb_env_obs_stats_update")
+            return
+        a = np.ascontiguousarray(ob, np.float32)
+        check(w.L.rsb_env_obs_stats_update(w.handle, _hp(a), nb, 0, RSB_HOST), "rsb_env_obs_stats_update")
+
+    def normalize_obs(self, ob, out=None, clip=0.0):
+        """[..., num_obs] observations normalised with the library's current statistics (rsb_env_obs_normalize): a stored rollout.  torch CUDA
+        tensors (out may be ob itself; nothing synchronises) or numpy arrays."""
+        w = self.world
+        if ob.shape[-1] != self.num_obs:
+            raise ValueError(f"normalize_obs: the last dimension must be {self.num_obs}")
+        rows = int(np.prod(ob.shape[:-1]))
+        if self._is_torch(ob):
+            import torch
+            self._check_tensor(ob, tuple(ob.shape), torch.float32, "ob")
+            out = torch.empty_like(ob) if out is None else out
+            self._check_tensor(out, tuple(ob.shape), torch.float32, "out")
+            check(w.L.rsb_env_obs_normalize(w.handle, C.c_void_p(ob.data_ptr()), C.c_void_p(out.data_ptr()), rows, float(clip), RSB_DEVICE), "rsb_env_obs_normalize")
+            return out
+        a = np.ascontiguousarray(ob, np.float32)
+        out = np.empty_like(a) if out is None else out
+        if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.shape == a.shape):
+            raise ValueError("normalize_obs: out must be a C-contiguous float32 array of ob's shape")
+        check(w.L.rsb_env_obs_normalize(w.handle, _hp(a), _hp(out), rows, float(clip), RSB_HOST), "rsb_env_obs_normalize")
+        return out
+
+    def obs_statistics(self):
+        """(mean [num_obs] float32, var [num_obs] float32, count float) of the library's running statistics (synchronises)"""
+        w = self.world
+        mean, var, count = np.zeros(self.num_obs, np.float32), np.zeros(self.num_obs, np.float32), C.c_double(0.0)
+        check(w.L.rsb_env_get_obs_stats(w.handle, _hp(mean), _hp(var), C.byref(count)), "rsb_env_get_obs_stats")
+        return mean, var, count.value
+
+    def set_obs_statistics(self, mean, var, count):
+        w = self.world
+        m, v = np.ascontiguousarray(mean, np.float32).reshape(-1), np.ascontiguousarray(var, np.float32).reshape(-1)
+        if m.shape != (self.num_obs,) or v.shape != (self.num_obs,):
+            raise ValueError(f"set_obs_statistics: mean and var must have {self.num_obs} entries")
+        check(w.L.rsb_env_set_obs_stats(w.handle, _hp(m), _hp(v), float(count)), "rsb_env_set_obs_stats")
+
+    def obs_statistics_device(self):
+        """device pointers (mean [num_obs], inv_std [num_obs]) of the library's statistics: valid for the env's lifetime, updated in stream order"""
+        w = self.world
+        m, s = C.c_void_p(0), C.c_void_p(0)
+        check(w.L.rsb_env_obs_stats_device(w.handle, C.byref(m), C.byref(s)), "rsb_env_obs_stats_device")
+        return int(m.value or 0), int(s.value or 0)
+
+    # -- running observation statistics in torch (RaisimGymVecEnv's normalize_ob / RunningMeanStd [RECALL]) -------------------
     def observe_normalized(self, out, update_statistics=True, clip=10.0, eps=1e-8):
         """Observation tensor [num_envs, num_obs] (torch CUDA), normalised in place with running mean / variance kept on
         the device (batched Welford update, as upstream's RunningMeanStd); returns `out`."""
