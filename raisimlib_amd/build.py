@@ -3,9 +3,9 @@
 `python -m raisimlib_amd.build` or `__graft_entry__.build()`.  hipcc cross-compiles without a GPU.
 The .so stays in-tree (raisimlib_amd/lib/) so it travels to the GPU box with the repo snapshot.
 
-The fused step kernel has ten (LPE, KMAX, CL, ML) classes x {production, profiling}; each instance is its own object
-(step_instance.hip + five -D macros, list in step_launch.h) and the objects are compiled in parallel, so a clean build
-takes about a minute on 8 cores instead of several in one translation unit.  Objects are cached under
+The fused step kernel has one instance per (LPE, KMAX, CL, ML) class of the list in step_launch.h (RSB_STEP_INSTANCES), plus a
+profiling twin where the list asks for one; each instance is its own object (step_instance.hip + five -D macros) and the objects
+are compiled in parallel instead of in one translation unit.  Objects are cached under
 raisimlib_amd/lib/obj/ and rebuilt when a source they depend on is newer.
 """
 import hashlib
@@ -48,10 +48,11 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 
 
 def step_instances():
-    """[(lpe, kmax, cl, ml)] parsed from the RSB_STEP_INSTANCES line of step_launch.h (single source of truth)."""
+    """[(lpe, kmax, cl, ml, prof)] parsed from the RSB_STEP_INSTANCES X-macro of step_launch.h (single source of truth); prof = 1: the class
+    also has a profiling twin."""
     txt = open(os.path.join(CSRC, "step_launch.h")).read()
-    line = re.search(r"RSB_STEP_INSTANCES:(.*)", txt).group(1)
-    return [tuple(int(x) for x in tok.split(",")) for tok in line.split()]
+    body = re.search(r"#define RSB_STEP_INSTANCES\(X\)((?:.*\\\n)*.*)", txt).group(1)
+    return [tuple(int(x) for x in m) for m in re.findall(r"X\((\d+),(\d+),(\d+),(\d+),([01])\)", body)]
 
 
 def source_hash(extra_flags=()):
@@ -95,8 +96,8 @@ def build(force=False, verbose=True, extra_flags=(), jobs=None):
     # RSB_BUILD_ONLY="16,8,0,4 32,16,0,12": kernel experiments rebuild these instances only; the other objects are linked as they are
     # (rsb_source_hash() then no longer describes the library: the test-suite refuses it - a full build() is what ships)
     only = {tuple(int(x) for x in tok.split(",")) for tok in os.environ.get("RSB_BUILD_ONLY", "").split()}
-    for lpe, kmax, cl, ml in step_instances():
-        for prof in ((0,) if cl & (18 | 64) else (0, 1)):     # (the peer-exchange, the pipelined and the resident classes have no profiling twin: rsb_world.hip, launch_step)
+    for lpe, kmax, cl, ml, twin in step_instances():
+        for prof in range(twin + 1):
             obj = os.path.join(OBJ, f"step_{lpe}_{kmax}_{cl}_{ml}_{prof}" + (f".{tag}" if tag else "") + ".o")
             objs.append(obj)
             if only and (lpe, kmax, cl, ml) not in only and os.path.exists(obj):

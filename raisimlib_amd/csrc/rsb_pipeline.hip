@@ -495,8 +495,7 @@ int closed_loop_resident(rsb_world* w, int K, const rsb_linear_policy* lin, cons
 // the conditions under which do_integrate launches a step of a closed-loop run on the pipeline (else it takes the world's stream - and joins, with the
 // action stage in flight: ADVICE r05).  Checked BEFORE the stage is launched; a run that fails the test stays in lock-step.
 bool closed_loop_can_pipeline(const rsb_world* w) {
-  static const bool poison = std::getenv("RSB_POISON_LDS") != nullptr;
-  return w->pipe_on && !w->d_prof && w->dbg_env < 0 && !poison && !w->peer.connected && !w->launch_mask && !(w->integ_rk4 && !w->rk4_inner);
+  return pipelining_allowed(w, w->peer.connected, w->launch_mask) && !(w->integ_rk4 && !w->rk4_inner);
 }
 
 int closed_loop_run_inner(rsb_world* w, int K, rsb_stage_launch_fn launch, void* user, const rsb_linear_policy* lin, const rsb_mlp_policy* mlp, long long pg0);
@@ -514,7 +513,10 @@ int closed_loop_run_inner(rsb_world* w, int K, rsb_stage_launch_fn launch, void*
   if (lin) { lin_copy = *lin; user = &lin_copy; launch = launch_linear_stage; }
   if (mlp) { mlp_copy = *mlp; user = &mlp_copy; launch = launch_mlp_stage; }
   if (w->res_on && (lin || mlp)) {     // (a caller-supplied stage cannot be compiled into the step kernel: it keeps the paths below)
-    if (resident_class(w, lin ? 1 : 2, mlp ? mlp_width(*mlp) : 0) >= 0) return closed_loop_resident(w, K, lin, mlp, pg0);
+    StepClass c;
+    LaunchKind k;
+    k.res_stage = lin ? 1 : 2; k.mlp_width = mlp ? mlp_width(*mlp) : 0;
+    if (choose_step_class(w, k, &c) == RSB_OK) return closed_loop_resident(w, K, lin, mlp, pg0);
   }
   if (!closed_loop_can_pipeline(w)) return closed_loop_lockstep(w, K, launch, user, pg0);
   // ---- pipelined: ONE launch of the stage for passes 0 .. K on its own stream, K step launches alternating between the two step streams
@@ -524,7 +526,7 @@ int closed_loop_run_inner(rsb_world* w, int K, rsb_stage_launch_fn launch, void*
   cl_fill_ctx(w, &c, K, pg0);
   int st = check_lpe(w, effective_lpe(w));
   if (st != RSB_OK) return st;
-  st = upload_image(w);          // (do_integrate would do it - and JOIN for it, with the stage already in flight)
+  st = upload_image(w, world_layout(w));          // (do_integrate would do it - and JOIN for it, with the stage already in flight)
   if (st != RSB_OK) return st;
   st = pipe_prepare(w, c.blocks);
   if (st != RSB_OK) return st;

@@ -86,11 +86,11 @@ const std::string& extra_flags() {
   return flags;
 }
 
-std::string key_line(const rsbw::SpecClass& c, const std::string& defs) {
+std::string key_line(const rsbw::StepClass& c, const std::string& defs) {
   return std::to_string(c.lpe) + " " + std::to_string(c.kmax) + " " + std::to_string(c.cl) + " " + std::to_string(c.ml) + (c.prof ? " p" : "") + " | " + defs;
 }
 
-std::string file_of(const rsbw::SpecClass& c, const std::string& defs) {
+std::string file_of(const rsbw::StepClass& c, const std::string& defs) {
   char buf[160];
   std::snprintf(buf, sizeof buf, "step_%d_%d_%d_%d%s_%016llx.hsaco", c.lpe, c.kmax, c.cl, c.ml, c.prof ? "p" : "",
                 (unsigned long long)fnv1a64(std::string(rsb_source_hash()) + " " + key_line(c, defs) + (extra_flags().empty() ? "" : " ## " + extra_flags())));
@@ -98,13 +98,13 @@ std::string file_of(const rsbw::SpecClass& c, const std::string& defs) {
 }
 
 // Itanium mangling of rsbk::rsb_step_kernel<LPE, KMAX, CL, ML, false>(rsbk::StepArgs)
-std::string symbol_of(const rsbw::SpecClass& c) {
+std::string symbol_of(const rsbw::StepClass& c) {
   char buf[160];
   std::snprintf(buf, sizeof buf, "_ZN4rsbk15rsb_step_kernelILi%dELi%dELi%dELi%dELb%dEEEvNS_8StepArgsE", c.lpe, c.kmax, c.cl, c.ml, c.prof ? 1 : 0);
   return buf;
 }
 
-bool parse_line(const char* line, rsbw::SpecClass& c, std::string& defs) {
+bool parse_line(const char* line, rsbw::StepClass& c, std::string& defs) {
   int n = 0;
   c.prof = 0;
   if (!line || std::sscanf(line, "%d %d %d %d %n", &c.lpe, &c.kmax, &c.cl, &c.ml, &n) != 4 || n == 0) return false;
@@ -119,7 +119,7 @@ bool parse_line(const char* line, rsbw::SpecClass& c, std::string& defs) {
   return true;
 }
 
-int compile(const rsbw::SpecClass& c, const std::string& defs) {
+int compile(const rsbw::StepClass& c, const std::string& defs) {
   const std::string dir = rsb_spec_dir(), out = dir + "/" + file_of(c, defs);
   if (file_exists(out)) return RSB_OK;
   ::mkdir(dir.c_str(), 0777);
@@ -155,7 +155,7 @@ void record_miss(const std::string& line) {
 }
 
 // loads <dir>/<file> on the current device; nullptr when it is absent or refused (said once on stderr)
-hipFunction_t load(int device, const rsbw::SpecClass& c, const std::string& defs) {
+hipFunction_t load(int device, const rsbw::StepClass& c, const std::string& defs) {
   const std::string file = file_of(c, defs), id = std::to_string(device) + ":" + file;
   Loaded& L = g_loaded[id];
   if (L.tried) return L.fn;
@@ -192,7 +192,7 @@ int spec_default_mode() {
   return RSB_SPEC_CACHED;
 }
 
-hipFunction_t spec_find(rsb_world* w, const SpecClass& c, const StepArgs& a) {
+hipFunction_t spec_find(rsb_world* w, const StepClass& c, const StepArgs& a) {
   if (w->spec_mode == RSB_SPEC_OFF) return nullptr;
   // the world's own memo: class + field values -> function (or nullptr), looked up at every launch
   std::array<int, 4 + rsbk::kSpecFields> k{};
@@ -235,13 +235,13 @@ const char* rsb_spec_dir(void) {
 }
 
 int rsb_spec_compile(const char* manifest_line) {
-  rsbw::SpecClass c; std::string defs;
+  rsbw::StepClass c; std::string defs;
   if (!parse_line(manifest_line, c, defs)) { rsb::set_error("rsb_spec_compile: expected '<lpe> <kmax> <cl> <ml> | -DRSB_SPECIALIZED -DRSB_SPEC_...=...'"); return RSB_E_INVALID; }
   return compile(c, defs);
 }
 
 int rsb_spec_file_name(const char* manifest_line, char* out, int capacity) {
-  rsbw::SpecClass c; std::string defs;
+  rsbw::StepClass c; std::string defs;
   if (!parse_line(manifest_line, c, defs) || !out || capacity <= 0) { rsb::set_error("rsb_spec_file_name: bad manifest line or buffer"); return RSB_E_INVALID; }
   std::snprintf(out, (size_t)capacity, "%s", file_of(c, defs).c_str());
   return RSB_OK;

@@ -47,6 +47,7 @@ struct rsb_world {
   std::vector<float> h_kp, h_kd;      // host mirror of the PD gains (baked into the image)
   std::vector<double> col_mu, col_rest, col_rthr;   // per-primitive overrides, < 0 = the world's default
   bool image_dirty = true;
+  LdsLayout image_layout{};           // the layout d_image was built for (upload_image rebuilds it for a launch of another one)
   // self-collision (rsb_set_self_collision): candidate primitive pairs i < j in enumeration order, body pairs the caller
   // excluded (rsb_ignore_collision_between), per-pair material overrides (< 0 = the world's default)
   bool self_collision = true;
@@ -190,15 +191,23 @@ struct rsb_world {
 
 // helpers shared by the translation units (rsb_world.hip unless noted)
 namespace rsbw {
+// a kernel class: the template arguments of rsbk::rsb_step_kernel a launch runs with (an entry of step_launch.h's RSB_STEP_INSTANCES; prof: its profiling twin)
+struct StepClass { int lpe, kmax, cl, ml, prof = 0; };
+// what a launch asks of the class beyond the world's configuration: the peer exchange in its epilogue, a pipelined twin, a resident launch
+// (res_stage 0 open loop, 1 linear policy, 2 actor network of greatest width mlp_width; -1 not resident)
+struct LaunchKind { bool peer = false, pipelined = false; int res_stage = -1, mlp_width = 0; };
+int choose_step_class(const rsb_world* w, const LaunchKind& k, StepClass* out);   // RSB_OK, or RSB_E_UNSUPPORTED with the reason in the error string
+bool instrumented(const rsb_world* w);                          // profiling / debug instrumentation is on: launches run the profiling twin
+bool pipelining_allowed(const rsb_world* w, bool peer, const uint8_t* mask);   // what a pipelined step launch needs of the world (do_integrate, closed loop)
+LdsLayout world_layout(const rsb_world* w);                     // the step kernel's LDS layout for this world as configured
 int do_integrate(rsb_world* w, int nsub);
-int upload_image(rsb_world* w);                                 // the step kernel's per-block tables, when a setter dirtied them (joins)
+int upload_image(rsb_world* w, const LdsLayout& L);            // the step kernel's per-block tables, when a setter dirtied them or L is new (joins)
 int effective_lpe(const rsb_world* w);
 int check_lpe(const rsb_world* w, int lpe);
 int copy_in(rsb_world* w, float* dst, const float* src, size_t n, int space);
 int copy_out(rsb_world* w, void* dst, const void* src, size_t bytes, int space);
 int launch_env_obs(rsb_world* w, float* dst, hipStream_t s);
 int launch_dynamics_query(rsb_world* w, hipStream_t s);           // M, h and M^-1 of the current state into d_M / d_h / d_Minv (the query kernels)
-int resident_class(rsb_world* w, int stage, int mlp_width);          // the resident kernel class (CL bits) of this world as configured, or -1 with the reason in the error string
 int rk4_integrate(rsb_world* w, int nsub);                        // rsb_rk4.hip     // the stand-alone env-task observation of the current state
 int obs_stats_init(rsb_world* w);                                 // rsb_obstats.hip: the observation statistics at their initial state (rsb_env_configure, once)
 void obs_stats_free(rsb_world* w);                                // rsb_obstats.hip (rsb_destroy)

@@ -157,23 +157,23 @@ static LdsLayout make_layout_pitch(const rsb_model_blob& b, int kcap, int n_self
   return L;
 }
 
+// dynamic LDS of a workgroup of 64 / lpe envs
+static size_t lds_bytes_of(const LdsLayout& L, int lpe) { return sizeof(float) * ((size_t)L.shared_total + (size_t)(64 / lpe) * L.per_env); }
+
 // The conflict-free pitch of the model table (step_types.h: kModelPitch) costs 4 floats per body - and a workgroup per CU where the layout sits on a 160-KiB
 // cliff (the Atlas-like humanoid at 32 lanes per env: 3 workgroups -> 2, config 5 fell from 38.9 M to 26.4 M env-steps/s in gpurun r06d): it is taken only
 // where no lanes-per-env choice loses a workgroup to it.
 LdsLayout make_layout(const rsb_model_blob& b, int kcap, int n_self) {
   const LdsLayout tight = make_layout_pitch(b, kcap, n_self, rsbk::kModelSlot), wide = make_layout_pitch(b, kcap, n_self, rsbk::kModelPitch);
   auto wgs = [](const LdsLayout& L, int lpe) {
-    const size_t bytes = sizeof(float) * ((size_t)L.shared_total + (size_t)(64 / lpe) * L.per_env);
+    const size_t bytes = lds_bytes_of(L, lpe);
     return bytes > 160 * 1024 ? 0 : (int)std::min<size_t>(4, (160 * 1024) / bytes);
   };
   for (int lpe : {16, 32, 64}) if (wgs(wide, lpe) != wgs(tight, lpe)) return tight;
   return wide;
 }
 
-size_t lds_bytes_for(const rsb_model_blob& b, int kcap, int lpe, int n_self) {
-  LdsLayout L = make_layout(b, kcap, n_self);
-  return sizeof(float) * ((size_t)L.shared_total + (size_t)(64 / lpe) * L.per_env);
-}
+size_t lds_bytes_for(const rsb_model_blob& b, int kcap, int lpe, int n_self) { return lds_bytes_of(make_layout(b, kcap, n_self), lpe); }
 
 // Lanes per env: the group size that keeps the most envs resident on a CU.  The kernel runs at one wave per SIMD
 // (register budget), so a CU holds min(4, 160 KiB / workgroup LDS) workgroups of 64/LPE envs each.  ANYmal-like models:
@@ -282,57 +282,34 @@ __global__ void env_reset_kernel(float* gc, float* gv, int32_t* count, int32_t* 
   count[e] = 0; flags[e] = 0;
 }
 
-template <int LPE, int KMAX, int CL, int ML>
-int launch_step(rsb_world* w, const StepArgs& a, size_t lds_bytes, bool prof) {
-  constexpr int EPW = 64 / LPE;
-  const int blocks = (w->N + EPW - 1) / EPW;
-  // the profiling instance carries the cycle stamps / contact-problem dump / LDS poisoning; production launches use the lean one
-  // (the peer-exchange classes, CL bit 2, are built without a profiling twin: profile the exchange-free class instead)
-  hipError_t e;
-  if constexpr ((CL & (18 | 64)) != 0) {
-    if (prof) { rsb::set_error("profiling / debug instrumentation is not built for the peer-exchange, the pipelined and the resident kernel classes: disconnect the exchange (rsb_obs_peer_destroy) / switch pipelining and residency off first"); return RSB_E_UNSUPPORTED; }
-    e = rsbk::launch_step_instance<LPE, KMAX, CL, ML, false>(a, blocks, lds_bytes, w->launch_stream);
-  } else {
-    e = prof ? rsbk::launch_step_instance<LPE, KMAX, CL, ML, true>(a, blocks, lds_bytes, w->launch_stream)
-             : rsbk::launch_step_instance<LPE, KMAX, CL, ML, false>(a, blocks, lds_bytes, w->launch_stream);
-  }
-  HIP_TRY(e);
+// ---- the instances of step_launch.h's list and their launchers; the class of a launch is looked up here (a scan of ~100 entries, no allocation)
+using StepLauncher = hipError_t (*)(const StepArgs&, int, size_t, hipStream_t);
+struct StepInstance { int lpe, kmax, cl, ml; StepLauncher run, run_prof; };   // (run_prof: the profiling twin, nullptr where the list builds none)
+template <int LPE, int KMAX, int CL, int ML, int PROF>
+constexpr StepInstance step_instance() {
+  if constexpr (PROF != 0) return {LPE, KMAX, CL, ML, &rsbk::launch_step_instance<LPE, KMAX, CL, ML, false>, &rsbk::launch_step_instance<LPE, KMAX, CL, ML, true>};
+  else return {LPE, KMAX, CL, ML, &rsbk::launch_step_instance<LPE, KMAX, CL, ML, false>, nullptr};
+}
+#define RSB_STEP_ENTRY(LPE, KMAX, CL, ML, PROF) step_instance<LPE, KMAX, CL, ML, PROF>(),
+constexpr StepInstance kStepInstances[] = {RSB_STEP_INSTANCES(RSB_STEP_ENTRY)};
+#undef RSB_STEP_ENTRY
+
+const StepInstance* find_instance(const StepClass& c) {
+  for (const StepInstance& e : kStepInstances)
+    if (e.lpe == c.lpe && e.kmax == c.kmax && e.cl == c.cl && e.ml == c.ml) return &e;
+  return nullptr;
+}
+
+// launches `blocks` workgroups of class c (chosen by choose_step_class, so a miss here is a bug)
+int launch_instance(const StepClass& c, const StepArgs& a, int blocks, size_t lds_bytes, hipStream_t stream) {
+  const StepInstance* e = find_instance(c);
+  const StepLauncher run = !e ? nullptr : c.prof ? e->run_prof : e->run;
+  if (!run) { rsb::set_error("internal: step kernel class <" + std::to_string(c.lpe) + ", " + std::to_string(c.kmax) + ", " + std::to_string(c.cl) + ", " + std::to_string(c.ml) + (c.prof ? ", profiling" : "") + "> is not built"); return RSB_E_UNSUPPORTED; }
+  HIP_TRY(run(a, blocks, lds_bytes, stream));
   return RSB_OK;
 }
 
-template <int KMAX, int CL, int ML>
-int launch_lpe_class(rsb_world* w, const StepArgs& a, size_t lds_bytes, int lpe, bool prof) {
-  if (lpe == 16) return launch_step<16, KMAX, CL, ML>(w, a, lds_bytes, prof);
-  if (lpe == 32) return launch_step<32, KMAX, CL, ML>(w, a, lds_bytes, prof);
-  return launch_step<64, KMAX, CL, ML>(w, a, lds_bytes, prof);
-}
-template <int KMAX, int CL, int ML>
-int launch_lpe(rsb_world* w, const StepArgs& a, size_t lds_bytes, int lpe, bool prof) {
-  if constexpr ((CL & 2) == 0) {     // a pipelined launch (StepArgs::pipe_prog) runs the class's pipelined twin: the plain instances carry none of its code
-    if (a.pipe_prog) return launch_lpe_class<KMAX, CL | 16, ML>(w, a, lds_bytes, lpe, prof);
-  }
-  return launch_lpe_class<KMAX, CL, ML>(w, a, lds_bytes, lpe, prof);
-}
-
 int n_self_pairs(const rsb_world* w) { return w->self_collision ? (int)w->self_pairs.size() / 2 : 0; }
-
-// ---- resident launches (StepArgs::res_steps; kernel classes | 64): compiled for the benchmark's two model sizes
-template <int CLR>
-int launch_resident_class(rsb_world* w, const StepArgs& a, size_t lds_bytes, bool quadruped) {
-  if (quadruped) return launch_step<16, 8, CLR, 4>(w, a, lds_bytes, false);
-  if constexpr (CLR == (64 | 384)) return RSB_E_UNSUPPORTED;      // (never reached: resident_class refuses it)
-  else return launch_step<32, 16, CLR, 12>(w, a, lds_bytes, false);
-}
-int launch_resident(rsb_world* w, const StepArgs& a, size_t lds_bytes, int cl, bool quadruped) {
-  switch (cl) {
-    case 64: return launch_resident_class<64>(w, a, lds_bytes, quadruped);
-    case 64 | 128: return launch_resident_class<64 | 128>(w, a, lds_bytes, quadruped);
-    case 64 | 256: return launch_resident_class<64 | 256>(w, a, lds_bytes, quadruped);
-    case 64 | 384: return launch_resident_class<64 | 384>(w, a, lds_bytes, quadruped);
-  }
-  rsb::set_error("internal: unknown resident kernel class");
-  return RSB_E_UNSUPPORTED;
-}
 
 }  // namespace rsbw
 extern "C" int rsb_model_lds_bytes(const rsb_model* m, int kmax, int self_collision, int lanes_per_env) {
@@ -357,34 +334,64 @@ int check_lpe(const rsb_world* w, int lpe) {
   return RSB_OK;
 }
 
-// The resident kernel class (CL bits) a launch of this world would run as it is configured now, or -1 with the reason in the error string.
-// stage: 0 open loop, 1 linear policy, 2 actor network of greatest width mlp_width.
-int resident_class(rsb_world* w, int stage, int mlp_width) {
-  auto no = [](const char* why) { rsb::set_error(std::string("no resident launch for this world: ") + why); return -1; };
-  const rsb_model_blob& b = w->blob;
-  const int lpe = effective_lpe(w), kcap = kcap_of(b, w->kmax), mlv = b.depth - 1;
-  if (b.fixed_base) return no("fixed-base systems");
-  if (w->peer.connected) return no("the peer-mapped obs exchange is connected");
-  if (w->integ_rk4 || w->integ_theta != 1.0) return no("an integration scheme other than SEMI_IMPLICIT");
-  if (w->slip_rule == RSB_SLIP_COULOMB) return no("RSB_SLIP_COULOMB");
-  if ((w->hm_contacts >= 2 || (w->hm_capsule && w->n_cap > 0)) && w->terrain_type == 1) return no("more than one contact per primitive against a height map");
-  if (w->d_prof || w->dbg_env >= 0 || std::getenv("RSB_POISON_LDS")) return no("profiling / debug instrumentation is active");
-  if (w->N % (64 / lpe) != 0) return no("the number of envs is not a multiple of the envs per workgroup");
-  const bool quad = mlv <= 4 && kcap == 8 && lpe == 16, humanoid = mlv <= 12 && kcap == 16 && lpe == 32;
-  if (!quad && !humanoid) return no("compiled for tree depth <= 5 / <= 8 contact slots / 16 lanes per env and for tree depth <= 13 / 16 slots / 32 lanes per env");
-  if (stage == 0) return 64;
-  if (stage == 1) return 64 | 128;
-  if (stage == 2) {
-    if (mlp_width <= 128) return 64 | 256;
-    if (mlp_width <= 256 && quad) return 64 | 384;
-    return no("actor-network widths above 128 (humanoid-sized models) / 256");
-  }
-  return no("unknown stage");
+bool instrumented(const rsb_world* w) {
+  static const bool poison = std::getenv("RSB_POISON_LDS") != nullptr;  // debug aid, see tests/test_gpu_properties.py
+  return w->d_prof || w->dbg_env >= 0 || poison;
 }
+
+// The kernel class a launch of this world runs: the features the world asks for as class bits (step_launch.h), the contact capacity and the
+// support-chain capacity (ML) of its tree depth, looked up in the instance list.  A class exists if and only if it is listed; a launch whose
+// class is not is refused with the reason of the feature that has none.
+int choose_step_class(const rsb_world* w, const LaunchKind& k, StepClass* out) {
+  const rsb_model_blob& b = w->blob;
+  const bool resident = k.res_stage >= 0;
+  const bool peer = resident ? w->peer.connected : k.peer;
+  const bool hm2 = (w->hm_contacts >= 2 || (w->hm_capsule && w->n_cap > 0)) && w->terrain_type == 1;   // more than one contact per primitive against a height map
+  const bool th = w->integ_theta != 1.0, coul = w->slip_rule == RSB_SLIP_COULOMB;
+  const int needs = (b.fixed_base ? 1 : 0) | (peer ? 2 : 0) | (hm2 ? 4 : 0) | (th ? 8 : 0) | (coul ? 32 : 0);
+  const int mlv = b.depth - 1;
+  StepClass c{effective_lpe(w), kcap_of(b, w->kmax), needs, mlv <= 4 ? 4 : mlv <= 12 ? 12 : mlv <= 16 ? 16 : 0, instrumented(w) ? 1 : 0};
+  if (resident) {
+    auto no = [](const char* why) { rsb::set_error(std::string("no resident launch for this world: ") + why); return RSB_E_UNSUPPORTED; };
+    if (w->integ_rk4) return no("an integration scheme other than SEMI_IMPLICIT");
+    if (c.prof) return no("profiling / debug instrumentation is active");
+    if (w->N % (64 / c.lpe) != 0) return no("the number of envs is not a multiple of the envs per workgroup");
+    const char* wide = "actor-network widths above 128 (humanoid-sized models) / 256";
+    if (k.res_stage > 2) return no("unknown stage");
+    if (k.res_stage == 2 && k.mlp_width > 256) return no(wide);
+    c.cl |= 64 | (k.res_stage == 0 ? 0 : k.res_stage == 1 ? 128 : k.mlp_width <= 128 ? 256 : 384);     // + the action stage inside (stage_bodies.h)
+    if (!find_instance(c)) {
+      if (needs) return no(needs & 1 ? "fixed-base systems" : needs & 2 ? "the peer-mapped obs exchange is connected" : needs & 8 ? "an integration scheme other than SEMI_IMPLICIT"
+                           : needs & 32 ? "RSB_SLIP_COULOMB" : "more than one contact per primitive against a height map");
+      if (c.cl == (64 | 384) && find_instance(StepClass{c.lpe, c.kmax, 64, c.ml})) return no(wide);
+      return no("compiled for tree depth <= 5 / <= 8 contact slots / 16 lanes per env and for tree depth <= 13 / 16 slots / 32 lanes per env");
+    }
+  } else {
+    if (k.pipelined && !(needs & 2)) c.cl |= 16;      // the class's pipelined twin (StepArgs::pipe_prog): the plain instances carry none of its code
+    const StepInstance* e = find_instance(c);
+    if (!e) {
+      rsb::set_error(th ? "integration schemes other than SEMI_IMPLICIT: built for floating-base systems of tree depth <= 13 without the peer-mapped obs exchange and with one contact per primitive"
+                     : coul ? "RSB_SLIP_COULOMB: built for floating-base systems of tree depth <= 5 with <= 8 contact slots, the default integration scheme, one contact per primitive, no peer-mapped obs exchange"
+                     : hm2 ? "two contacts per primitive against a height map: built for floating-base systems of tree depth <= 13 without the peer-mapped obs exchange"
+                     : peer ? "the peer-mapped obs exchange is compiled for floating-base models of tree depth <= 13"
+                     : "model outside the compiled kernel classes (tree depth <= 17)");
+      return RSB_E_UNSUPPORTED;
+    }
+    // the profiling instance carries the cycle stamps / contact-problem dump / LDS poisoning; production launches use the lean one
+    if (c.prof && !e->run_prof) { rsb::set_error("profiling / debug instrumentation is not built for the peer-exchange, the pipelined and the resident kernel classes: disconnect the exchange (rsb_obs_peer_destroy) / switch pipelining and residency off first"); return RSB_E_UNSUPPORTED; }
+  }
+  *out = c;
+  return RSB_OK;
+}
+
+// what a pipelined step launch needs of the world: pipelining on, no instrumentation (the twins have no profiling build), no peer exchange, no env mask
+bool pipelining_allowed(const rsb_world* w, bool peer, const uint8_t* mask) { return w->pipe_on && !instrumented(w) && !peer && !mask; }
+
+LdsLayout world_layout(const rsb_world* w) { return make_layout(w->blob, kcap_of(w->blob, w->kmax), n_self_pairs(w)); }
 
 // The per-block tables of the step kernel exactly as they sit in LDS (LdsLayout::t_*): the kernel copies this image with
 // float4 loads instead of staging ten tables one latency-bound loop at a time.  Rebuilt when a setter changes what it bakes
-// in: PD gains, control mode, contact materials.  (The layout of the shared tables does not depend on the contact capacity.)
+// in: PD gains, control mode, contact materials - and for a launch of another layout (the model table's pitch follows the contact capacity: make_layout).
 std::vector<float> build_lds_image(const rsb_world* w, const LdsLayout& L) {
   const rsb_model_blob& b = w->blob;
   auto dm = std::make_unique<DevModel>();
@@ -422,12 +429,12 @@ std::vector<float> build_lds_image(const rsb_world* w, const LdsLayout& L) {
   return img;
 }
 
-// the step kernel's per-block tables (build_lds_image) and the self-collision pairs' materials, re-uploaded when a setter dirtied them.
-// Joins (stream_of): callers that must not join later - a closed-loop run with its action stage in flight - call it up front.
-int upload_image(rsb_world* w) {
-  if (!w->image_dirty) return RSB_OK;
-  const int kcap = kcap_of(w->blob, w->kmax);
-    std::vector<float> img = build_lds_image(w, make_layout(w->blob, kcap, n_self_pairs(w)));
+// the step kernel's per-block tables (build_lds_image) in layout L and the self-collision pairs' materials, re-uploaded when a setter dirtied them
+// or the image was built for another layout.  Joins (stream_of): callers that must not join later - a closed-loop run with its action stage in
+// flight - call it up front.
+int upload_image(rsb_world* w, const LdsLayout& L) {
+  if (!w->image_dirty && std::memcmp(&L, &w->image_layout, sizeof L) == 0) return RSB_OK;
+    std::vector<float> img = build_lds_image(w, L);
     HIP_TRY(hipMemcpyAsync(w->d_image, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice, stream_of(w)));
     const int np = n_self_pairs(w);
     std::vector<float> mat((size_t)4 * np, 0.f);
@@ -447,16 +454,40 @@ int upload_image(rsb_world* w) {
     }
     HIP_TRY(hipStreamSynchronize(stream_of(w)));   // img / mat are stack-lifetime buffers
     w->image_dirty = false;
+    w->image_layout = L;
   return RSB_OK;
 }
 
 int do_integrate(rsb_world* w, int nsub) {
   HIP_TRY(hipSetDevice(w->device));
   if (w->integ_rk4 && !w->rk4_inner) return rk4_integrate(w, nsub);      // IntegrationScheme::RUNGE_KUTTA_4: host-driven over the query kernels (rsb_rk4.hip)
-  const int lpe = effective_lpe(w);
-  int st = check_lpe(w, lpe);
+  // what this launch fuses and its env mask: taken off the world first, so that a refused launch leaves neither to the next one
+  const rsb_world::Fuse f = w->fuse;
+  w->fuse = rsb_world::Fuse();
+  const uint8_t* const mask = w->launch_mask;
+  w->launch_mask = nullptr;
+  int st = check_lpe(w, effective_lpe(w));
   if (st != RSB_OK) return st;
-  const int kcap = kcap_of(w->blob, w->kmax);
+  // the kernel class: a resident launch runs K control steps in this ONE launch; a pipelined one goes to one of the two private streams, behind a
+  // gate that lets it start only when the launch before it (on the other stream) has been dispatched completely - its workgroups wait for their
+  // predecessors' envs (open loop) or for the action stage's rows (closed loop), which therefore must all be running or done (no deadlock: a waiting
+  // workgroup never keeps a predecessor off the chip).  rsb_pipeline.hip holds the bookkeeping.
+  const bool resident = f.res_steps > 0;
+  const bool closed_loop = f.closed_loop;      // a step of rsb_closed_loop_run: waits for the action stage's word instead of its predecessor's
+  LaunchKind kind;
+  kind.peer = f.peer;
+  kind.pipelined = !resident && f.pipeline && (!f.env_task || closed_loop) && pipelining_allowed(w, f.peer, mask);
+  if (resident) {
+    kind.res_stage = f.res_stage;
+    if (f.res_stage == 2) for (int l = 0; l <= f.res_mlp.n_layers; ++l) kind.mlp_width = std::max(kind.mlp_width, (int)f.res_mlp.dims[l]);
+  }
+  StepClass c;
+  st = choose_step_class(w, kind, &c);
+  if (st != RSB_OK) return st;
+  if (resident && mask) { rsb::set_error("no resident launch with an env mask"); return RSB_E_UNSUPPORTED; }
+  const LdsLayout L = world_layout(w);
+  const size_t lds_bytes = lds_bytes_of(L, c.lpe);
+  const int blocks = (w->N + 64 / c.lpe - 1) / (64 / c.lpe);
   StepArgs a;
   std::memset(&a, 0, sizeof a);
   a.model = w->d_model;
@@ -471,39 +502,20 @@ int do_integrate(rsb_world* w, int nsub) {
   a.heights = w->d_heights;
   a.hm_index = w->d_hm_index;
   a.warm = w->warm_start ? w->d_warm : nullptr;
-  st = upload_image(w);
+  st = upload_image(w, L);
   if (st != RSB_OK) return st;
   a.lds_image = w->d_image;
-  if (w->fuse.ptarget_src) { a.ptarget = w->fuse.ptarget_src; a.ptarget_store = w->d_pt; }
-  if (w->fuse.act) { a.act = w->fuse.act; a.act_mean = w->d_env_mean; a.act_std = w->env_cfg.action_std; a.ptarget_store = w->d_pt; a.tau2_out = w->d_env_tau2; }
+  if (f.ptarget_src) { a.ptarget = f.ptarget_src; a.ptarget_store = w->d_pt; }
+  if (f.act) { a.act = f.act; a.act_mean = w->d_env_mean; a.act_std = w->env_cfg.action_std; a.ptarget_store = w->d_pt; a.tau2_out = w->d_env_tau2; }
   uint8_t* env_done = nullptr;
-  if (w->fuse.env_task) {   // rsb_env_step: reward, termination, reset and the next observation in this launch's epilogue
-    a.env_reward = w->fuse.env_reward; a.env_ob = w->fuse.env_ob; env_done = w->fuse.env_done;
+  if (f.env_task) {   // rsb_env_step: reward, termination, reset and the next observation in this launch's epilogue
+    a.env_reward = f.env_reward; a.env_ob = f.env_ob; env_done = f.env_done;
     a.env_fwd_coeff = w->env_cfg.forward_vel_coeff; a.env_fwd_clip = w->env_cfg.forward_vel_clip;
     a.env_torque_coeff = w->env_cfg.torque_coeff; a.env_terminal_reward = w->env_cfg.terminal_reward;
     a.tau2_out = nullptr;
   }
-  a.obs_out = w->fuse.obs_out; a.obs_idx = w->fuse.obs_idx; a.obs_slots = w->fuse.obs_slots;
-  const bool peer = w->fuse.peer;
-  // a second contact per primitive against a height map (rsb_set_heightmap_contacts): a kernel class of its own, floating base, no peer exchange
-  // an integration scheme other than semi-implicit Euler (rsb_set_integration_scheme): likewise a class of its own
-  const bool th = w->integ_theta != 1.0;
-  if (th && (w->blob.fixed_base || peer || ((w->hm_contacts >= 2 || (w->hm_capsule && w->n_cap > 0)) && w->terrain_type == 1) || w->blob.depth - 1 > 12)) {
-    rsb::set_error("integration schemes other than SEMI_IMPLICIT: built for floating-base systems of tree depth <= 13 without the peer-mapped obs exchange and with one contact per primitive");
-    return RSB_E_UNSUPPORTED;
-  }
-  // the classical Coulomb slip rule (rsb_set_slip_rule): a kernel class of its own (bit 32), built for the quadruped-sized models
-  const bool coul = w->slip_rule == RSB_SLIP_COULOMB;
-  if (coul && (w->blob.fixed_base || peer || th || w->blob.depth - 1 > 4 || kcap != 8 || ((w->hm_contacts >= 2 || (w->hm_capsule && w->n_cap > 0)) && w->terrain_type == 1))) {
-    rsb::set_error("RSB_SLIP_COULOMB: built for floating-base systems of tree depth <= 5 with <= 8 contact slots, the default integration scheme, one contact per primitive, no peer-mapped obs exchange");
-    return RSB_E_UNSUPPORTED;
-  }
-  const bool hm2 = (w->hm_contacts >= 2 || (w->hm_capsule && w->n_cap > 0)) && w->terrain_type == 1;   // class-4 kernels: more than one contact per primitive against a height map
-  if (hm2 && (w->blob.fixed_base || peer || w->blob.depth - 1 > 12)) {
-    rsb::set_error("two contacts per primitive against a height map: built for floating-base systems of tree depth <= 13 without the peer-mapped obs exchange");
-    return RSB_E_UNSUPPORTED;
-  }
-  if (peer) {   // rsb_control_step with the peer-mapped obs exchange connected: rows go to every rank's gathered buffer of this step's parity
+  a.obs_out = f.obs_out; a.obs_idx = f.obs_idx; a.obs_slots = f.obs_slots;
+  if (f.peer) {   // rsb_control_step with the peer-mapped obs exchange connected: rows go to every rank's gathered buffer of this step's parity
     rsb_world::Peer& P = w->peer;
     const uint32_t step = ++P.step;
     const int par = (int)(step & 1u);
@@ -517,17 +529,10 @@ int do_integrate(rsb_world* w, int nsub) {
     a.n_obs_peers = P.ranks; a.obs_row0 = P.rank * w->N; a.obs_step = step;
     a.obs_slots = P.slots; a.obs_idx = P.idx.empty() ? nullptr : P.d_idx;
   }
-  a.early_term = (w->early_term && w->fuse.have_allowed) ? 1 : 0;
-  a.do_reset = w->fuse.do_reset; a.allowed = w->fuse.allowed; a.gc0 = w->fuse.gc0; a.gv0 = w->fuse.gv0; a.reset_rows = w->fuse.rows;
+  a.early_term = (w->early_term && f.have_allowed) ? 1 : 0;
+  a.do_reset = f.do_reset; a.allowed = f.allowed; a.gc0 = f.gc0; a.gv0 = f.gv0; a.reset_rows = f.rows;
   if (!a.do_reset) { a.gc0 = w->d_gc; a.gv0 = w->d_gv; a.reset_rows = w->N; }   // never dereferenced, but keep the pointers valid
-  // resident launch: K control steps in this ONE launch (the caller has checked resident_class)
-  int res_cl = -1;
-  if (w->fuse.res_steps > 0) {
-    const rsb_world::Fuse& f = w->fuse;
-    int width = 0;
-    if (f.res_stage == 2) for (int l = 0; l <= f.res_mlp.n_layers; ++l) width = std::max(width, (int)f.res_mlp.dims[l]);
-    res_cl = resident_class(w, f.res_stage, width);
-    if (res_cl < 0 || w->launch_mask) { w->fuse = rsb_world::Fuse(); w->launch_mask = nullptr; if (res_cl >= 0) rsb::set_error("no resident launch with an env mask"); return RSB_E_UNSUPPORTED; }
+  if (resident) {
     a.res_steps = f.res_steps; a.res_full = w->res_full ? 1 : 0;
     a.res_targets = f.res_targets; a.res_period = f.res_period; a.res_first = f.res_first;
     a.res_obs_stride = f.res_obs_stride; a.res_done_stride = f.res_done_stride; a.res_pass_global0 = f.res_pass_global0;
@@ -535,18 +540,12 @@ int do_integrate(rsb_world* w, int nsub) {
     if (f.res_stage == 2) a.res_pol.mlp = f.res_mlp;
     if (f.res_stage == 0) { a.ptarget = f.res_targets + (size_t)(f.res_first % f.res_period) * ((size_t)w->N * w->blob.nq); a.ptarget_store = w->d_pt; }
   }
-  uint8_t* res_done = w->fuse.res_done;
-  const int res_steps = std::max(w->fuse.res_steps, 1);
-  const bool closed_loop = w->fuse.closed_loop;      // a step of rsb_closed_loop_run: waits for the action stage's word instead of its predecessor's
-  const bool pipe_ok = w->fuse.pipeline && (!w->fuse.env_task || closed_loop);
-  const rsb_world::Fuse fuse_in = w->fuse;
-  w->fuse = rsb_world::Fuse();
   a.prof = w->d_prof;
   a.dbg = w->dbg_env >= 0 ? w->d_dbg : nullptr;
   a.dbg_env = w->dbg_env;
   a.N = w->N; a.nsub = nsub; a.kmax = w->kmax; a.control_mode = w->control_mode;
   a.nb = w->blob.nb; a.nq = w->blob.nq; a.nv = w->blob.nv; a.ncol = w->blob.ncol; a.depth = w->blob.depth;
-  a.cw = round4(6 + w->blob.depth - 1); a.max_kid = w->max_kid; a.fixed_base = w->blob.fixed_base; a.chain = (w->chain && lpe == 16) ? 1 : 0;
+  a.cw = round4(6 + w->blob.depth - 1); a.max_kid = w->max_kid; a.fixed_base = w->blob.fixed_base; a.chain = (w->chain && c.lpe == 16) ? 1 : 0;
   a.dt = (float)w->dt; a.gx = (float)w->gravity[0]; a.gy = (float)w->gravity[1]; a.gz = (float)w->gravity[2];
   a.mu = (float)w->mu; a.erp = (float)w->erp;
   a.alpha_init = (float)w->alpha_init; a.alpha_min = (float)w->alpha_min; a.alpha_decay = (float)w->alpha_decay;
@@ -566,30 +565,22 @@ int do_integrate(rsb_world* w, int nsub) {
     a.hm_max = w->hm_max;
   }
   a.n_self = n_self_pairs(w); a.self_mat = w->d_self_mat;
-  a.L = make_layout(w->blob, kcap, a.n_self);
-  const size_t lds_bytes = lds_bytes_for(w->blob, kcap, lpe, n_self_pairs(w));
+  a.L = L;
   static const bool poison = std::getenv("RSB_POISON_LDS") != nullptr;  // debug aid, see tests/test_gpu_properties.py
   a.poison_lds = poison ? 1 : 0;
   static const bool prof_fine = std::getenv("RSB_PROF_FINE") != nullptr;  // debug aid: also time searches / Newton steps / epilogues
   a.prof_fine = prof_fine ? 1 : 0;
   a.lds_floats = (int)(lds_bytes / sizeof(float));
-  const bool prof = a.prof != nullptr || a.dbg != nullptr || a.poison_lds != 0;
-  a.done_out = env_done ? env_done : res_done ? res_done : w->d_done_out;
+  a.done_out = env_done ? env_done : f.res_done ? f.res_done : w->d_done_out;
   a.tau_out = w->want_genf ? w->d_genf : nullptr;
-  a.env_mask = w->launch_mask; w->launch_mask = nullptr;
-  // ---- pipelined control steps: this launch goes to one of the two private streams, behind a gate that lets it start only when the launch
-  // before it (on the other stream) has been dispatched completely - its workgroups wait for their predecessors' envs (open loop) or for the
-  // action stage's rows (closed loop), which therefore must all be running or done (no deadlock: a waiting workgroup never keeps a
-  // predecessor off the chip).  rsb_pipeline.hip holds the bookkeeping.
+  a.env_mask = mask;
   hipStream_t ls = nullptr;
-  const bool pipelined = w->pipe_on && pipe_ok && !prof && !peer && !a.env_mask && res_cl < 0;
-  if (pipelined) {
-    const int blocks = (w->N + (64 / lpe) - 1) / (64 / lpe);
+  if (kind.pipelined) {
     st = pipe_begin_launch(w, a, blocks, closed_loop, &ls);
     if (st != RSB_OK) return st;
     if (!w->pipe_log_suppress) {      // what a faulted pipeline replays in lock-step (pipe_recover)
       rsb_world::PipeLog e;
-      e.f = fuse_in; e.nsub = nsub; e.done_out = w->d_done_out;
+      e.f = f; e.nsub = nsub; e.done_out = w->d_done_out;
       w->pipe_log.push_back(e);
     }
     w->pipe_time_logged += nsub * w->dt;
@@ -602,53 +593,18 @@ int do_integrate(rsb_world* w, int nsub) {
   const bool rec = w->timing && (w->launch_index++ % w->timing_stride == 0);
   if (rec && !w->ring0.empty()) { e0 = w->ring0[w->ring_next]; e1 = w->ring1[w->ring_next]; }
   if (rec) HIP_TRY(hipEventRecord(e0, ls));
-  // kernel classes by the deepest body level (support-chain capacity of the contact-column / Delassus phases) and by the base (fixed-base systems have a class of their own)
-  const int mlv = w->blob.depth - 1;
-  // a specialised code object of the class this launch is about to run (rsb_spec.hip): same kernel, the model's dimensions and the world's switches as constants
-  hipFunction_t spec_fn = nullptr;
-  if (w->spec_mode != RSB_SPEC_OFF && mlv <= 16 && !(prof && (res_cl >= 0 || peer || a.pipe_prog))) {   // (the classes without a profiling twin refuse `prof` below)
-    rsbw::SpecClass sc{lpe, kcap, 0, mlv <= 4 ? 4 : mlv <= 12 ? 12 : 16};
-    if (res_cl >= 0) sc = mlv <= 4 ? rsbw::SpecClass{16, 8, res_cl, 4} : rsbw::SpecClass{32, 16, res_cl, 12};
-    else {
-      if (mlv > 4) sc.kmax = 16;
-      sc.cl = w->blob.fixed_base ? 1 : (coul && mlv <= 4) ? 32 : (hm2 && mlv <= 12) ? 4 : (th && mlv <= 12) ? 8 : (peer && mlv <= 12) ? 2 : 0;
-      if (coul && mlv <= 4) sc.kmax = 8;
-      if (!(sc.cl & 2) && a.pipe_prog) sc.cl |= 16;     // the class's pipelined twin (launch_lpe)
-    }
-    sc.prof = prof ? 1 : 0;
-    spec_fn = rsbw::spec_find(w, sc, a);
-  }
-  if (spec_fn) {
-    const int epw = 64 / (res_cl >= 0 ? (mlv <= 4 ? 16 : 32) : lpe);
-    st = rsbw::spec_launch(spec_fn, a, (w->N + epw - 1) / epw, lds_bytes, w->launch_stream);
-    if (st == RSB_OK) { ++w->spec_launches; if (res_cl >= 0) ++w->res_launches; }
-  } else if (res_cl >= 0) {
-    st = launch_resident(w, a, lds_bytes, res_cl, mlv <= 4);
-    if (st == RSB_OK) { ++w->res_launches; ++w->generic_launches; }
-  } else if (mlv <= 4) {
-    if (w->blob.fixed_base) st = kcap == 8 ? launch_lpe<8, 1, 4>(w, a, lds_bytes, lpe, prof) : launch_lpe<16, 1, 4>(w, a, lds_bytes, lpe, prof);
-    else if (coul) st = launch_lpe<8, 32, 4>(w, a, lds_bytes, lpe, prof);
-    else if (hm2) st = kcap == 8 ? launch_lpe<8, 4, 4>(w, a, lds_bytes, lpe, prof) : launch_lpe<16, 4, 4>(w, a, lds_bytes, lpe, prof);
-    else if (th) st = kcap == 8 ? launch_lpe<8, 8, 4>(w, a, lds_bytes, lpe, prof) : launch_lpe<16, 8, 4>(w, a, lds_bytes, lpe, prof);
-    else if (peer) st = kcap == 8 ? launch_lpe<8, 2, 4>(w, a, lds_bytes, lpe, prof) : launch_lpe<16, 2, 4>(w, a, lds_bytes, lpe, prof);
-    else st = kcap == 8 ? launch_lpe<8, 0, 4>(w, a, lds_bytes, lpe, prof) : launch_lpe<16, 0, 4>(w, a, lds_bytes, lpe, prof);
-  } else if (mlv <= 12) {
-    st = w->blob.fixed_base ? launch_lpe<16, 1, 12>(w, a, lds_bytes, lpe, prof) : hm2 ? launch_lpe<16, 4, 12>(w, a, lds_bytes, lpe, prof)
-         : th ? launch_lpe<16, 8, 12>(w, a, lds_bytes, lpe, prof) : peer ? launch_lpe<16, 2, 12>(w, a, lds_bytes, lpe, prof) : launch_lpe<16, 0, 12>(w, a, lds_bytes, lpe, prof);
-  } else if (mlv <= 16) {
-    st = w->blob.fixed_base ? launch_lpe<16, 1, 16>(w, a, lds_bytes, lpe, prof) : launch_lpe<16, 0, 16>(w, a, lds_bytes, lpe, prof);
-  } else {
-    rsb::set_error("model outside the compiled kernel classes (tree depth <= 17)");
-    return RSB_E_UNSUPPORTED;
-  }
+  // a specialised code object of the class (rsb_spec.hip): same kernel, the model's dimensions and the world's switches as constants; else the ahead-of-time instance
+  const hipFunction_t spec_fn = spec_find(w, c, a);
+  st = spec_fn ? spec_launch(spec_fn, a, blocks, lds_bytes, ls) : launch_instance(c, a, blocks, lds_bytes, ls);
   if (st != RSB_OK) return st;
-  if (!spec_fn && res_cl < 0) ++w->generic_launches;
-  if (pipelined) pipe_end_launch(w, a, ls);
+  ++(spec_fn ? w->spec_launches : w->generic_launches);
+  if (resident) ++w->res_launches;
+  if (kind.pipelined) pipe_end_launch(w, a, ls);
   if (rec) {
     HIP_TRY(hipEventRecord(e1, ls));
     if (!w->ring0.empty()) { w->ring_next = (w->ring_next + 1) % w->ring0.size(); if (w->ring_count < w->ring0.size()) ++w->ring_count; }
   }
-  w->world_time += (double)res_steps * nsub * w->dt;
+  w->world_time += (double)std::max(f.res_steps, 1) * nsub * w->dt;
   w->integrate1_valid = false;
   // (the fused epilogue left the observation the NEXT step starts from in the world's own buffer - unless the caller holds raw pointers to the state rows
   //  and may write through them behind the library's back: then every closed-loop run recomputes its first observation, as the lock-step path does)
@@ -1464,12 +1420,19 @@ int rsb_control_step(rsb_world* w, const float* p_target, const float* d_target,
     return RSB_E_INVALID;
   }
   HIP_TRY(hipSetDevice(w->device));
+  if (w->peer.connected) {     // (refused before anything is written: whether the exchange has a kernel class for this world)
+    StepClass c;
+    LaunchKind k;
+    k.peer = true;
+    int st = check_lpe(w, effective_lpe(w));
+    if (st == RSB_OK) st = choose_step_class(w, k, &c);
+    if (st != RSB_OK) return st;
+  }
   if (d_target) { int st = copy_in(w, w->d_dt, d_target, (size_t)w->N * w->blob.nv, RSB_DEVICE); if (st) return st; w->dt_zero = false; }
   rsb_world::Fuse f;
   f.ptarget_src = p_target;   // read in place by the launch, which also refreshes the world's own copy
   f.pipeline = p_target != nullptr && d_target == nullptr;   // (rsb_set_step_pipelining: control steps that upload nothing may overlap)
   if (w->peer.connected) {
-    if (w->blob.fixed_base || w->blob.depth - 1 > 12) { rsb::set_error("rsb_control_step: the peer-mapped obs exchange is compiled for floating-base models of tree depth <= 13"); return RSB_E_UNSUPPORTED; }
     if (obs_out && n_force_slots != w->peer.slots) { rsb::set_error("rsb_control_step: obs_out must use the force slots the peer exchange was created with"); return RSB_E_INVALID; }
     if (obs_out) {   // ... and the same primitives in them: the launch writes ONE obs row layout to the caller's block and to the peers'
       for (int i = 0; i < n_force_slots; ++i) {
@@ -1511,7 +1474,10 @@ int rsb_control_steps(rsb_world* w, int n_steps, const float* p_targets, int per
   }
   HIP_TRY(hipSetDevice(w->device));
   const size_t slice = (size_t)w->N * w->blob.nq;
-  if (!(w->res_on && resident_class(w, 0, 0) >= 0)) {
+  StepClass c;
+  LaunchKind open_loop;
+  open_loop.res_stage = 0;
+  if (!(w->res_on && choose_step_class(w, open_loop, &c) == RSB_OK)) {
     uint8_t* const saved = w->d_done_out;
     int st = RSB_OK;
     for (int j = 0; j < n_steps && st == RSB_OK; ++j) {
@@ -1552,7 +1518,10 @@ int rsb_set_step_residency(rsb_world* w, int on) {
 int rsb_step_residency_enabled(const rsb_world* w) { return w && w->res_on ? 1 : 0; }
 int rsb_step_residency_status(rsb_world* w, int stage) {
   if (!w) { rsb::set_error("rsb_step_residency_status: null world"); return 0; }
-  return resident_class(w, stage, 128) >= 0 ? 1 : 0;
+  StepClass c;
+  LaunchKind k;
+  k.res_stage = stage; k.mlp_width = 128;
+  return stage >= 0 && choose_step_class(w, k, &c) == RSB_OK ? 1 : 0;
 }
 long long rsb_step_residency_launches(const rsb_world* w) { return w ? w->res_launches : 0; }
 int rsb_debug_resident_full_writes(rsb_world* w, int on) {

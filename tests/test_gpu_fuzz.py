@@ -138,3 +138,31 @@ def test_random_tree_three_substeps_on_a_height_map(built_lib, seed):
     eu = np.abs(u1 - ref["u"]).max(axis=1) / (1 + np.abs(ref["u"]).max(axis=1))
     assert np.isfinite(q1).all() and conv.mean() > 0.5
     assert np.median(eu) < 5e-5 and np.percentile(eu[conv], 95) < 5e-3, (seed, np.median(eu), np.percentile(eu[conv], 95))
+
+
+def test_a_new_contact_capacity_rebuilds_the_lds_image(built_lib):
+    """rsb_set_max_contacts after a world has stepped: the model table's pitch in LDS follows the contact capacity (make_layout; this tree: 36 floats
+    per body at 8 slots, 32 at 16), so the next launch rebuilds the kernel's image of the tables for its own layout.  From the same state, the world
+    then steps exactly as one that ran at 16 slots from the start (the image used to keep the old pitch)."""
+    rng = np.random.default_rng(6)
+    model = Model(urdf_string=random_urdf(rng, int(rng.integers(8, 17))))
+    assert model.blob.depth - 1 <= 4      # (deeper trees always run at 16 slots)
+    nq, nv, N = model.nq, model.nv, 64
+    gc = np.zeros((N, nq)); gc[:, 0:2] = rng.uniform(-1, 1, (N, 2)); gc[:, 2] = rng.uniform(0.0, 0.5, N)
+    qq = rng.normal(size=(N, 4)); gc[:, 3:7] = qq / np.linalg.norm(qq, axis=1, keepdims=True)
+    gc[:, 7:] = rng.uniform(-0.5, 0.5, (N, nq - 7))
+    gv = rng.normal(size=(N, nv))
+    kp = np.zeros(nv, np.float32); kd = np.zeros(nv, np.float32); kp[6:] = 30.0; kd[6:] = 0.5
+    a, b = BatchedWorld(model, N), BatchedWorld(model, N)
+    for w in (a, b):
+        w.set_self_collision(False); w.set_solver_warm_start(False)
+        w.set_pd_gains(kp, kd); w.set_pd_target(gc, np.zeros((N, nv)))
+    a.set_max_contacts(8); a.set_state(gc, gv)
+    a.integrate(1)
+    a.set_max_contacts(16); b.set_max_contacts(16)
+    q, u = a.get_state()
+    b.set_state(q, u)
+    a.integrate(2); b.integrate(2)
+    (qa, ua), (qb, ub) = a.get_state(), b.get_state()
+    a.close(); b.close()
+    assert np.isfinite(qa).all() and np.array_equal(qa, qb) and np.array_equal(ua, ub)

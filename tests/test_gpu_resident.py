@@ -105,6 +105,17 @@ def test_resident_equals_pipelined_and_falls_back_outside_its_classes(built_lib)
     co.run(5)
     assert co.w.residency_launches() == 0
     co.w.close()
+    # a quadruped-sized model (tree depth <= 5) at 16 contact slots and 32 lanes per env: no resident class is built for it (the humanoid's
+    # <32, 16, 64, 12> is compiled for deeper trees), so its control steps run as separate launches
+    wide, ref = Open(2, 1024, True), Open(2, 1024, False)
+    for o in (wide, ref):
+        o.w.set_max_contacts(16)
+        o.w.set_lanes_per_env(32)
+    assert not wide.w.residency_status(0)
+    oa, da = ref.run(10)
+    ob, db = wide.run(10)
+    assert ref.torch.equal(oa, ob) and ref.torch.equal(da, db) and wide.w.residency_launches() == 0
+    wide.w.close(); ref.w.close()
 
 
 @pytest.mark.parametrize("stage,n,lpe,runs,K", [("linear", 4096, 0, 10, 100), ("mlp", 4096, 0, 10, 100), ("linear", 1000, 0, 3, 40), ("mlp", 1000, 0, 2, 30)])
