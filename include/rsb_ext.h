@@ -179,6 +179,11 @@ int rsb_debug_resident_full_writes(rsb_world* w, int on);
  * (4 x 40 048 B for the ANYmal-like model, 3 workgroups for the Atlas-like one), and a table that grows by a few hundred bytes can cost a quarter or a third of the
  * resident waves (tests/test_kernel_budget.py pins the counts). */
 int rsb_model_lds_bytes(const rsb_model* m, int kmax, int self_collision, int lanes_per_env);
+/* host only (no GPU): does the step kernel run the up pass of this model on four lanes per body (specialised code objects, 16 lanes per env, <= 8 contact
+ * slots)?  It does for a base with four consecutively numbered serial chains of equal length, <= 16 bodies - every tree level below the base then holds four bodies.
+ * Returns the number of levels below the base and fills table[(level - 1) * 4 + quad] with the body that quad works on (table may be NULL; capacity in ints), 0 for
+ * every other model (the lane = body loop runs), < 0 on error. */
+int rsb_model_up_quads(const rsb_model* m, int* table, int capacity);
 
 /* ---- specialised step kernels.  The ahead-of-time kernel classes read the model's dimensions (bodies, coordinates, tree depth, collision primitives,
  * self-collision pairs) and the world's switches (terrain kind, sub-steps per call, warm start, solver lags) from their kernel arguments.  A SPECIALISED code

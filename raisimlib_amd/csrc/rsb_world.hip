@@ -100,6 +100,26 @@ std::vector<int> enumerate_self_pairs(const rsb_model_blob& b, const std::vector
   return out;
 }
 
+// Quad form of the up pass (step_spec.h: RSB_UP_QUADS; step_phase_tree_up.inc).  A model qualifies when it is a base + FOUR consecutively numbered serial
+// chains of equal length, at most 16 bodies: every tree level below the base then holds exactly four bodies, and the body of quad g (lanes 4 g .. 4 g + 3 of a
+// 16-lane env) at level lv is  (g-th child of the base) + lv - 1.  Returns the number of levels below the base and fills table[(lv - 1) * 4 + g] (may be null), or 0.
+int up_quad_table(const rsb_model_blob& b, int* table) {
+  if (b.nb > 16 || b.depth < 2 || b.nb - 1 != 4 * (b.depth - 1)) return 0;
+  int first[4], n1 = 0;
+  for (int i = 1; i < b.nb; ++i) {
+    if (b.level[i] == 1) { if (n1 == 4) return 0; first[n1++] = i; }
+    else if (b.parent[i] != i - 1) return 0;
+  }
+  if (n1 != 4) return 0;
+  for (int g = 0; g < 4; ++g)
+    for (int lv = 1; lv < b.depth; ++lv) {
+      const int body = first[g] + lv - 1;
+      if (body >= b.nb || b.level[body] != lv) return 0;
+      if (table) table[(lv - 1) * 4 + g] = body;
+    }
+  return b.depth - 1;
+}
+
 // slots of the height-map narrow phase: one per primitive (every sphere of the model may be near the ground at once - a robot lying in a hollow)
 int hm_slots_for(const rsb_model_blob& b) { return std::max(rsbk::kHmSlots, (int)b.ncol); }
 
@@ -318,6 +338,14 @@ extern "C" int rsb_model_lds_bytes(const rsb_model* m, int kmax, int self_collis
   const int n_self = self_collision ? (int)rsbw::enumerate_self_pairs(b, std::vector<uint8_t>()).size() / 2 : 0;
   const int lpe = lanes_per_env ? lanes_per_env : rsbw::default_lpe(b, kmax, n_self);
   return (int)rsbw::lds_bytes_for(b, rsbw::kcap_of(b, kmax), lpe, n_self);
+}
+extern "C" int rsb_model_up_quads(const rsb_model* m, int* table, int capacity) {
+  if (!m) { rsb::set_error("rsb_model_up_quads: null model"); return RSB_E_INVALID; }
+  int t[16];
+  const int levels = rsbw::up_quad_table(m->blob, t);
+  if (table && capacity < 4 * levels) { rsb::set_error("rsb_model_up_quads: table too small"); return RSB_E_INVALID; }
+  if (table) for (int i = 0; i < 4 * levels; ++i) table[i] = t[i];
+  return levels;
 }
 namespace rsbw {
 int effective_lpe(const rsb_world* w) {
@@ -546,6 +574,8 @@ int do_integrate(rsb_world* w, int nsub) {
   a.N = w->N; a.nsub = nsub; a.kmax = w->kmax; a.control_mode = w->control_mode;
   a.nb = w->blob.nb; a.nq = w->blob.nq; a.nv = w->blob.nv; a.ncol = w->blob.ncol; a.depth = w->blob.depth;
   a.cw = round4(6 + w->blob.depth - 1); a.max_kid = w->max_kid; a.fixed_base = w->blob.fixed_base; a.chain = (w->chain && c.lpe == 16) ? 1 : 0;
+  // (2: the quad form of the up pass - its 48-float hand-over slots need the square Delassus layout's rows to themselves: the packed layout keeps the joint factors there)
+  if (a.chain && c.kmax <= 8 && up_quad_table(w->blob, nullptr) > 0 && w->blob.nb * rsbk::kUpQuadSlot <= L.ginv - L.g) a.chain = 2;
   a.dt = (float)w->dt; a.gx = (float)w->gravity[0]; a.gy = (float)w->gravity[1]; a.gz = (float)w->gravity[2];
   a.mu = (float)w->mu; a.erp = (float)w->erp;
   a.alpha_init = (float)w->alpha_init; a.alpha_min = (float)w->alpha_min; a.alpha_decay = (float)w->alpha_decay;

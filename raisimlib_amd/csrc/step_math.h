@@ -60,6 +60,15 @@ __device__ __forceinline__ void rigid_expand(const float* I10, float* IA) {
   IA[sym6(4, 0)] = -mc[2]; IA[sym6(4, 1)] = 0.f;    IA[sym6(4, 2)] = mc[0];  IA[sym6(4, 3)] = 0.f; IA[sym6(4, 4)] = m;
   IA[sym6(5, 0)] = mc[1];  IA[sym6(5, 1)] = -mc[0]; IA[sym6(5, 2)] = 0.f;    IA[sym6(5, 3)] = 0.f; IA[sym6(5, 4)] = 0.f; IA[sym6(5, 5)] = m;
 }
+// lane K of every quad (four consecutive lanes) -> the four lanes of that quad (DPP quad_perm)
+template <int K>
+__device__ __forceinline__ float quad_bcast(float x) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), K * 0x55, 0xf, 0xf, true));
+}
+// every lane takes the value of the lane four below it in its 16-lane row (DPP row_shr:4; lanes 0..3 of a row: zero)
+__device__ __forceinline__ float row_shr4(float x) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x114, 0xf, 0xf, true));
+}
 __device__ __forceinline__ void ld4(const float* p, float* o) {
   float4 v = *reinterpret_cast<const float4*>(p);
   o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;

@@ -49,6 +49,16 @@
     // serial chains numbered consecutively (StepArgs::chain): the parent of a body of level >= 2 is the lane below - its delta-velocity arrives by a DPP row
     // shift (six moves) instead of through the parent's BODY slot (two stores, the barrier, two loads: two LDS round trips per level of a lone wave)
     {
+#if RSB_UP_QUADS
+      // (quad form of the up pass: no body lane holds its joint's factors in registers - they come back from the FACT slot, which holds the same bits)
+      float bUD[6], brsD;
+      {
+        float Fk[16];
+        ldv<4>(FACT + bb * kFactSlot, Fk);
+        RSB_UNROLL for (int i = 0; i < 6; ++i) bUD[i] = Fk[6 + i];
+        brsD = Fk[12];
+      }
+#endif
       float an[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};    // this body's own delta-velocity once its level has run
       RSB_UNROLL for (int lv = 1; lv < RSB_SPEC_DEPTH; ++lv) {
         float ap[6];

@@ -17,12 +17,26 @@
   X(N_SELF, a.n_self) X(NSUB, a.nsub) X(KMAX, a.kmax) X(HAS_WARM, (a.warm != nullptr)) X(TERRAIN, a.terrain_type)                      \
   X(EARLY_TERM, (a.early_term != 0)) X(SECTION_ROUNDS, a.section_rounds) X(STALL_WINDOW, a.stall_window) X(FREEZE_AFTER, a.freeze_after) \
   X(REFINE, a.refine) X(MULTI_FA, a.multi_freeze_after) X(MULTI_DEPTH, a.multi_depth) X(MULTI_LIGHT, a.multi_light)                    \
-  X(MULTI_SW, a.multi_stall_window) X(CHAIN, (a.chain != 0)) X(MODEL_PITCH, a.L.model_pitch)
+  X(MULTI_SW, a.multi_stall_window) X(CHAIN, (a.chain != 0)) X(MODEL_PITCH, a.L.model_pitch) \
+  X(UP_QUADS, (a.chain == 2))
 
 #ifdef RSB_SPECIALIZED
 #define RSB_DIM(NAME, expr) (RSB_SPEC_##NAME)
 #else
 #define RSB_DIM(NAME, expr) (expr)
+#endif
+
+// Quad form of the up pass's level loop (step_phase_tree_up.inc): four lanes per body instead of one, in the specialised code objects of worlds whose
+// every tree level holds exactly four bodies at 16 lanes per env (StepArgs::chain == 2: the quadruped).  -DRSB_X_NO_UP_QUADS (RSB_SPEC_EXTRA_DEFS,
+// tools/exp/ab_defs.sh) compiles the lane = body loop of every other world instead: same results bit for bit (tests/test_gpu_up_quads.py).  The ahead-of-time
+// classes always run the lane = body loop.
+#if defined(RSB_SPECIALIZED) && RSB_SPEC_UP_QUADS && !defined(RSB_X_NO_UP_QUADS)
+#define RSB_UP_QUADS 1
+#if !RSB_SPEC_CHAIN
+#error "RSB_SPEC_UP_QUADS: the quad form of the up pass is for consecutively numbered chains (RSB_SPEC_CHAIN)"
+#endif
+#else
+#define RSB_UP_QUADS 0
 #endif
 
 namespace rsbk {

@@ -24,6 +24,12 @@ constexpr int kMaxC = RSB_MAX_COLLISIONS;
 #endif
 constexpr int kBodySlot = RSB_X_BODYSLOT;    // R9 r3 V6 A6 (A is reused for the delta-velocity of the final pass) [+ pad]
 constexpr int kUpSlot = RSB_X_UPSLOT;        // Ia21 Zc6 pad   (one per body)
+#ifndef RSB_X_UPQSLOT
+#define RSB_X_UPQSLOT 52
+#endif
+constexpr int kUpQuadSlot = RSB_X_UPQSLOT;   // quad form of the up pass (step_spec.h: RSB_UP_QUADS): the hand-over slot as six FULL rows on an 8-float pitch, row r = Ia[r][0..5] Zc[r] pad,
+                                  // + 4 floats: with 52 the body lanes' 16-byte stores of a row (lane = body) and the quad lanes' reads of their rows fall on different banks
+                                  // (with the rows' own 48 the eight lanes of a store group share two four-bank groups)
 constexpr int kEnvPad = RSB_X_ENVPAD;        // floats added to an env's LDS region (shifts the banks the wave's envs start on)
 constexpr int kFactSlot = 16;    // S6 UD6 rsD invD pad2
 constexpr int kConSlot = 16;     // x3 depth | t1 body | t2 col | n pad
@@ -140,7 +146,9 @@ struct StepArgs {
   int N, nsub, kmax, control_mode;
   int nb, nq, nv, ncol, depth, cw, max_kid, fixed_base;   // model dimensions (DevModel's, repeated here: see the kernel's first lines)
   int chain;                   // the tree is the base + serial chains numbered consecutively (every body of level >= 2 has parent = itself - 1) and fits a 16-lane row:
-                               // specialised code objects then hand a body's results to its child by a DPP row shift instead of through LDS (step_spec.h)
+                               // specialised code objects then hand a body's results to its child by a DPP row shift instead of through LDS (step_spec.h).
+                               // 2: ... and the chains are four of equal length (every level below the base holds exactly four bodies, rsb_world.hip:
+                               // up_quad_table): specialised code objects run the up pass's level loop on four lanes per body (RSB_UP_QUADS)
   float dt, gx, gy, gz, mu, erp;
   float alpha_init, alpha_min, alpha_decay, threshold;
   int max_iter, section_rounds, stall_window, freeze_after, refine;

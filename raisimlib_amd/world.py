@@ -79,6 +79,15 @@ class Model:
         check(min(n, 0), "rsb_model_lds_bytes")
         return n
 
+    def up_quads(self):
+        """Bodies the quads of a 16-lane env work on in the up pass, one list of four per tree level below the base, or [] where the lane = body loop runs
+        (host only; rsb_model_up_quads)"""
+        import ctypes
+        t = (ctypes.c_int * 16)()
+        n = lib().rsb_model_up_quads(self.handle, t, 16)
+        check(min(n, 0), "rsb_model_up_quads")
+        return [[int(t[4 * lv + g]) for g in range(4)] for lv in range(n)]
+
     def collision_indices(self, suffix):
         return [i for i, n in enumerate(self.collision_names()) if n.endswith(suffix)]
 
