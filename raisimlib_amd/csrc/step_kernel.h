@@ -105,6 +105,27 @@ __device__ __forceinline__ void body_inertia(const float* Rb, const float* rb, c
   RSB_UNROLL for (int i = 0; i < 3; ++i) { Zout[i] = dt * (IAc[i] + n1[i] + n2[i]); Zout[3 + i] = dt * (IAc[3 + i] + n3[i]); }
 }
 
+// ---- readers of a BODY slot (R9 r3 V6 A6).  With the quad form of the down pass (step_spec.h: RSB_DOWN_QUADS) three lanes of a quad write a slot, lane q the
+// entries of index q: [R q0 q1 q2, r q] x 3 | [Vw q, Vl q] x 3 | [Aw q, Al q] x 3 - the same reads, the registers named differently
+__device__ __forceinline__ void body_pose_ld(const float* slot, float* P) {      // P = R9 r3
+#if RSB_DOWN_QUADS
+  float T[12];
+  ldv<3>(slot, T);
+  RSB_UNROLL for (int i = 0; i < 3; ++i) { P[3 * i] = T[4 * i]; P[3 * i + 1] = T[4 * i + 1]; P[3 * i + 2] = T[4 * i + 2]; P[9 + i] = T[4 * i + 3]; }
+#else
+  ldv<3>(slot, P);
+#endif
+}
+__device__ __forceinline__ void body_vel_ld(const float* slot, float* Vb) {      // Vb[0..5] = V6 (Vb holds 8 floats)
+#if RSB_DOWN_QUADS
+  float T[8];
+  ld4(slot + 12, T); T[4] = slot[16]; T[5] = slot[17];
+  RSB_UNROLL for (int i = 0; i < 3; ++i) { Vb[i] = T[2 * i]; Vb[3 + i] = T[2 * i + 1]; }
+#else
+  ld4(slot + 12, Vb); Vb[4] = slot[16]; Vb[5] = slot[17];
+#endif
+}
+
 // ---- Delassus storage of the large-contact classes (KMAX > 8): only the blocks (i, j) with i >= j exist, packed at
 // ((i (i + 1)) / 2 + j) * 12 floats (3 rows on a 4-float pitch): 1632 floats at KMAX 16 where the square layout takes 3264 -
 // what lets a 31-body humanoid run two envs per wave (LPE 32).  tri_load returns M[ra][rb] = G[3 a + ra][3 b + rb] for any

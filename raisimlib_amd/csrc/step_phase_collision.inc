@@ -26,7 +26,7 @@
       cbody = __float_as_int(ct[4]);
       rad = ct[3];
       float P[12];
-      ldv<3>(BODY + cbody * kBodySlot, P);
+      body_pose_ld(BODY + cbody * kBodySlot, P);
       const float pl[3] = {ct[0], ct[1], ct[2]};
       float t[3];
       mat3_vec(P, pl, t);
@@ -58,7 +58,7 @@
           const int cic = min(t * LPE + s, ncol - 1);      // (clamped: no load is predicated)
           ld4(COLT + kColSlot * cic, ct[t]); ct[t][4] = COLT[kColSlot * cic + 4]; ld4(COLT + kColSlot * cic + 8, ax[t]);
         }
-        RSB_UNROLL for (int t = 0; t < NT; ++t) ldv<3>(BODY + __float_as_int(ct[t][4]) * kBodySlot, P[t]);
+        RSB_UNROLL for (int t = 0; t < NT; ++t) body_pose_ld(BODY + __float_as_int(ct[t][4]) * kBodySlot, P[t]);
         float pc[NT][3], pdep[NT];
         bool phit[NT];
         RSB_UNROLL for (int t = 0; t < NT; ++t) {
@@ -261,7 +261,7 @@
               const int cbody = __float_as_int(COLT[kColSlot * ci + 4]);
               {
                 float P[12], c0[4], ck[4], t0[3], tk[3];
-                ldv<3>(BODY + cbody * kBodySlot, P);
+                body_pose_ld(BODY + cbody * kBodySlot, P);
                 ld4(COLT + kColSlot * ci, c0);
                 mat3_vec(P, c0, t0);
                 RSB_UNROLL for (int a = 0; a < 3; ++a) {
@@ -404,7 +404,7 @@
               cbody = __float_as_int(COLT[kColSlot * ci + 4]);
               const float rim = COLT[kColSlot * ci + 11];
               rad = rim > 0.f ? rim : ct[3];          // a cylinder's ends are rim primitives (radius 0, rim = the cylinder's radius): COLT holds the cap CENTRES
-              ldv<3>(BODY + cbody * kBodySlot, P);
+              body_pose_ld(BODY + cbody * kBodySlot, P);
               mat3_vec(P, ct, t);
               ca[0] = P[9] + t[0]; ca[1] = P[10] + t[1]; ca[2] = P[11] + t[2];
               ld4(COLT + kColSlot * ce, ct);

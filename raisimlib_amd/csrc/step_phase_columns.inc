@@ -38,7 +38,7 @@
             }
           }
           float Vb[8];
-          ld4(BODY + kb * kBodySlot + 12, Vb); Vb[4] = BODY[kb * kBodySlot + 16]; Vb[5] = BODY[kb * kBodySlot + 17];
+          body_vel_ld(BODY + kb * kBodySlot, Vb);
           float Fres[6], wxx[3];
           cross3(x, t, Fres);
           Fres[3] = t[0]; Fres[4] = t[1]; Fres[5] = t[2];

@@ -52,11 +52,17 @@
 #if RSB_UP_QUADS
       // (quad form of the up pass: no body lane holds its joint's factors in registers - they come back from the FACT slot, which holds the same bits)
       float bUD[6], brsD;
+#if RSB_DOWN_QUADS
+      float bS[6];
+#endif
       {
         float Fk[16];
         ldv<4>(FACT + bb * kFactSlot, Fk);
         RSB_UNROLL for (int i = 0; i < 6; ++i) bUD[i] = Fk[6 + i];
         brsD = Fk[12];
+#if RSB_DOWN_QUADS
+        RSB_UNROLL for (int i = 0; i < 6; ++i) bS[i] = Fk[i];      // (quad form of the down pass: the joint axis too)
+#endif
       }
 #endif
       float an[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};    // this body's own delta-velocity once its level has run

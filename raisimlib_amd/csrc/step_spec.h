@@ -39,6 +39,16 @@
 #define RSB_UP_QUADS 0
 #endif
 
+// Quad form of the down pass's level loop (step_phase_tree_down.inc), for the same worlds and code objects: quad g walks DOWN chain g with the parent's pose,
+// velocity and bias acceleration in its registers and writes the BODY slots lane by lane (step_kernel.h: body_pose_ld); the update pass then takes the joint axis S
+// from the FACT slot, as it takes the up pass's factors there (hence: only beside the up pass's quad form).
+// -DRSB_X_NO_DOWN_QUADS compiles the lane = body loop beside the up pass's quad form: same results bit for bit (tests/test_gpu_down_quads.py).
+#if RSB_UP_QUADS && !defined(RSB_X_NO_DOWN_QUADS)
+#define RSB_DOWN_QUADS 1
+#else
+#define RSB_DOWN_QUADS 0
+#endif
+
 namespace rsbk {
 #define RSB_SPEC_COUNT_ONE(NAME, expr) +1
 constexpr int kSpecFields = 0 RSB_SPEC_FIELDS(RSB_SPEC_COUNT_ONE);

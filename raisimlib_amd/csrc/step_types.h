@@ -30,7 +30,10 @@ constexpr int kUpSlot = RSB_X_UPSLOT;        // Ia21 Zc6 pad   (one per body)
 constexpr int kUpQuadSlot = RSB_X_UPQSLOT;   // quad form of the up pass (step_spec.h: RSB_UP_QUADS): the hand-over slot as six FULL rows on an 8-float pitch, row r = Ia[r][0..5] Zc[r] pad,
                                   // + 4 floats: with 52 the body lanes' 16-byte stores of a row (lane = body) and the quad lanes' reads of their rows fall on different banks
                                   // (with the rows' own 48 the eight lanes of a store group share two four-bank groups)
-constexpr int kEnvPad = RSB_X_ENVPAD;        // floats added to an env's LDS region (shifts the banks the wave's envs start on)
+constexpr int kDownQuadSlot = 12;            // quad form of the down pass (step_spec.h: RSB_DOWN_QUADS): what a body lane parks for the quad that walks its chain: E9 q qd pad (all finite; aliases
+                                  // the front of the up pass's slots in the Delassus rows - consumed before those are written)
+static_assert(kDownQuadSlot <= kUpQuadSlot, "the down pass's staging slots lie inside the region the host checks for the up pass's (rsb_world.hip: nb * kUpQuadSlot <= L.ginv - L.g)");
+constexpr int kEnvPad = RSB_X_ENVPAD;       // floats added to an env's LDS region (shifts the banks the wave's envs start on)
 constexpr int kFactSlot = 16;    // S6 UD6 rsD invD pad2
 constexpr int kConSlot = 16;     // x3 depth | t1 body | t2 col | n pad
 constexpr int kColSlot = 12;     // per collision primitive in LDS: centre3 radius | body mu restitution res_threshold | axis3 rim (rim > 0: see rsb_model_blob::col_rim)
