@@ -237,6 +237,27 @@ class BatchedWorld {
   void getMassMatrices(float* M) { std::lock_guard<std::recursive_mutex> lk(mu_); RSB_CHECK(rsb_get_mass_matrix(world_, M, RSB_HOST)); }
   void getInverseMassMatrices(float* Mi) { std::lock_guard<std::recursive_mutex> lk(mu_); RSB_CHECK(rsb_get_inverse_mass_matrix(world_, Mi, RSB_HOST)); }
   void getNonlinearitiesAll(float* h) { std::lock_guard<std::recursive_mutex> lk(mu_); RSB_CHECK(rsb_get_nonlinearities(world_, h, RSB_HOST)); }
+  /// The frame accessors of ArticulatedSystem (getFramePosition / getFrameOrientation / getFrameVelocity / getFrameAngularVelocity, and
+  /// getPosition / getVelocity of a point of a body) for ALL envs in one call, computed on the device from the resident state; rows staged
+  /// through the per-env views are uploaded first.  frames: {body, offset in the body frame}.  Host buffers, any may be null (not all):
+  /// pos [N,F,3], rot [N,F,9] row-major world<-body, linVel [N,F,3], angVel [N,F,3], world frame.
+  void getFrameKinematics(const std::vector<rsb_frame>& frames, float* pos, float* rot, float* linVel, float* angVel) {
+    std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
+    RSB_CHECK(rsb_get_frame_kinematics(world_, frames.data(), (int)frames.size(), pos, rot, linVel, angVel, RSB_HOST));
+  }
+  /// getDenseFrameJacobian / getDenseFrameRotationalJacobian for all envs: Jlin, Jrot [N,F,3,dof()] (either may be null); a fixed-base
+  /// system keeps its six (zero) base columns here, as everywhere on the batch
+  void getFrameJacobians(const std::vector<rsb_frame>& frames, float* Jlin, float* Jrot) {
+    std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
+    RSB_CHECK(rsb_get_frame_jacobians(world_, frames.data(), (int)frames.size(), Jlin, Jrot, RSB_HOST));
+  }
+  /// setExternalForce / setExternalTorque for all envs: adds J^T force[e] + Jrot^T torque[e] (world frame, [N,3] each, either may be null)
+  /// to the feed-forward row of every env with mask[e] != 0 (null: all).  Same lifetime as the per-env calls: until setGeneralizedForce / clearExternalForces.
+  void addExternalWrench(const rsb_frame& frame, const float* force, const float* torque, const uint8_t* mask = nullptr) {
+    std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
+    RSB_CHECK(rsb_add_external_wrench(world_, &frame, force, torque, mask, RSB_HOST));
+    dropStage(RSB_F_TAU_FF);      // the host mirror of the feed-forward rows is refetched on its next use
+  }
 
   // batched, caller-owned host buffers (row-major [N, dim] float32, the raisimGymTorch matrix layout)
   void setState(const float* gc, const float* gv) {

@@ -27,6 +27,10 @@
  *   rsb_get_contacts                    <- ArticulatedSystem::getContacts() (contact/Contact.hpp, absent)
  *   rsb_get_mass_matrix / rsb_get_nonlinearities
  *                                       <- ArticulatedSystem::getMassMatrix()/getNonlinearities()
+ *   rsb_get_frame_kinematics / rsb_get_frame_jacobians / rsb_add_external_wrench
+ *                                       <- ArticulatedSystem::getFramePosition/getFrameOrientation/getFrameVelocity/
+ *                                          getFrameAngularVelocity/getDenseFrameJacobian/getDenseFrameRotationalJacobian/
+ *                                          setExternalForce/setExternalTorque, for all envs in one call
  *   rsb_gather_obs                      <- (new) the (q, u, contact-force) observation block that
  *                                          VectorizedEnvironment::observe() is built from
  *   rsb_env_observe_normalized / rsb_env_get_obs_stats / rsb_env_set_obs_stats
@@ -257,6 +261,26 @@ int rsb_get_inverse_mass_matrix(rsb_world* w, float* Minv, int space);
 int rsb_get_flags(rsb_world* w, int32_t* flags, int space);
 /* iterations the contact solver used in the last sub-step, [N] int32 */
 int rsb_get_solver_iterations(rsb_world* w, int32_t* iters, int space);
+
+/* Frame kinematics of ALL envs in one call, from the resident state [RECALL upstream's per-object ArticulatedSystem::getFramePosition /
+ * getFrameOrientation / getFrameVelocity / getFrameAngularVelocity / getPosition(body, pointB) / getVelocity(body, pointB)]: HIP kernels on the
+ * world's stream (ordered with lock-step, pipelined and resident steps); the RSB_DEVICE forms do not synchronise, the RSB_HOST forms stage through
+ * a device buffer the world owns.  frames: HOST array of n_frames (1..RSB_MAX_FRAMES) rsb_frame, passed to the kernel by value - no upload, no
+ * registered state.  Outputs in `space`, any may be NULL (not all), row-major float32:
+ *   pos [N,F,3] world; rot [N,F,9] row-major world<-body (what getFrameOrientation returns);
+ *   lin_vel [N,F,3] world velocity of the point; ang_vel [N,F,3] world angular velocity of the body.
+ * The base quaternion is normalised first, as the step kernel does.  Fixed-base model: the base does not move, whatever the base entries of gv hold. */
+int rsb_get_frame_kinematics(rsb_world* w, const rsb_frame* frames, int n_frames,
+                             float* pos, float* rot, float* lin_vel, float* ang_vel, int space);
+/* getDenseFrameJacobian / getDenseFrameRotationalJacobian of all envs: J_lin, J_rot [N,F,3,nv] (either may be NULL): lin_vel = J_lin gv,
+ * ang_vel = J_rot gv, gv in this ABI's order (base linear, base angular, joints).  Fixed-base model: nv columns as everywhere in this ABI,
+ * the six base columns zero. */
+int rsb_get_frame_jacobians(rsb_world* w, const rsb_frame* frames, int n_frames, float* J_lin, float* J_rot, int space);
+/* setExternalForce / setExternalTorque of all envs: tau_ff[e] += J_lin(e)^T force[e] + J_rot(e)^T torque[e] for every env with mask[e] != 0
+ * (mask NULL: all), J at the CURRENT state; force / torque [N,3] world frame and mask uint8 [N] in `space`, force or torque may be NULL (not both).
+ * It stays in RSB_F_TAU_FF until rsb_set_generalized_force replaces it (upstream clears external forces after every integrate()). */
+int rsb_add_external_wrench(rsb_world* w, const rsb_frame* frame, const float* force, const float* torque,
+                            const uint8_t* mask, int space);
 
 /* obs block [N, nq+nv+3*n_force_slots] = (q, u, contact force on chosen collision primitives).
  * collision_indices: host array of n_force_slots collision-primitive indices (e.g. the feet);

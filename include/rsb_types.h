@@ -111,6 +111,11 @@ typedef enum rsb_field {
   RSB_F_GENERALIZED_FORCE = 8   /* output only, see rsb_enable_generalized_force_output */
 } rsb_field;
 
+/* A point fixed in a body, for the batched frame queries (rsb_get_frame_kinematics, rsb_get_frame_jacobians, rsb_add_external_wrench):
+ * `offset` is expressed in the body's (joint) frame; {b, {0, 0, 0}} is what upstream calls the frame of body b. */
+#define RSB_MAX_FRAMES 64         /* = RSB_MAX_BODIES: "every body" is one call */
+typedef struct rsb_frame { int32_t body; float offset[3]; } rsb_frame;
+
 #define RSB_MAX_RANKS 8           /* ranks of one node (peer-mapped obs exchange, rsb.h) */
 
 #ifdef __cplusplus

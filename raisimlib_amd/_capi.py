@@ -43,6 +43,14 @@ class Contact(C.Structure):
                 ("depth", C.c_float), ("body", C.c_int32), ("collision", C.c_int32)]
 
 
+class Frame(C.Structure):
+    """rsb_frame: a point fixed in a body, offset in the body (joint) frame"""
+    _fields_ = [("body", C.c_int32), ("offset", C.c_float * 3)]
+
+
+RSB_MAX_FRAMES = 64
+
+
 class TerrainProperties(C.Structure):
     """rsb_terrain_properties (raisim::TerrainProperties field meaning)"""
     _fields_ = [("frequency", C.c_double), ("z_scale", C.c_double), ("x_size", C.c_double), ("y_size", C.c_double),
@@ -188,6 +196,9 @@ PROTOTYPES = {
     "rsb_get_inverse_mass_matrix": (_I, [_VP, _FP, _I]),
     "rsb_get_flags": (_I, [_VP, _FP, _I]),
     "rsb_get_solver_iterations": (_I, [_VP, _FP, _I]),
+    "rsb_get_frame_kinematics": (_I, [_VP, C.POINTER(Frame), _I, _FP, _FP, _FP, _FP, _I]),
+    "rsb_get_frame_jacobians": (_I, [_VP, C.POINTER(Frame), _I, _FP, _FP, _I]),
+    "rsb_add_external_wrench": (_I, [_VP, C.POINTER(Frame), _FP, _FP, _FP, _I]),
     "rsb_obs_dim": (_I, [_VP, _I]),
     "rsb_gather_obs": (_I, [_VP, _FP, _FP, _I, _I]),
     "rsb_reset_terminated": (_I, [_VP, _FP, _I, _FP, _FP, _I, _FP, _I]),

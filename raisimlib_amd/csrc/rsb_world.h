@@ -129,6 +129,8 @@ struct rsb_world {
   // normaliser and an MLP stage read, and the fold's scratch: block partials and batch moments (obs_part_batches batches of them)
   double* d_obs_stats = nullptr; float* d_obs_view = nullptr; double* d_obs_part = nullptr;
   int obs_part_batches = 0;
+  // batched frame queries (rsb_frames.hip): staging of the RSB_HOST forms' outputs / wrench inputs, grown on demand
+  float* d_frames_io = nullptr; size_t frames_io_cap = 0;
   std::vector<hipEvent_t> ring0, ring1;   // event pairs around the most recent step-kernel launches (rsb_enable_timing(w, n))
   size_t ring_next = 0, ring_count = 0;
   int timing_stride = 1;       // events bracket every timing_stride-th launch only (an event pair costs ~7 us of stream time)
@@ -211,6 +213,7 @@ int launch_dynamics_query(rsb_world* w, hipStream_t s);           // M, h and M^
 int rk4_integrate(rsb_world* w, int nsub);                        // rsb_rk4.hip     // the stand-alone env-task observation of the current state
 int obs_stats_init(rsb_world* w);                                 // rsb_obstats.hip: the observation statistics at their initial state (rsb_env_configure, once)
 void obs_stats_free(rsb_world* w);                                // rsb_obstats.hip (rsb_destroy)
+void frames_free(rsb_world* w);                                   // rsb_frames.hip (rsb_destroy)
 // rsb_pipeline.hip
 hipStream_t stream_of(rsb_world* w);                              // the world's stream for any use other than a pipelined launch (joins first)
 int pipe_join(rsb_world* w);

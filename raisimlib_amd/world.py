@@ -442,6 +442,106 @@ class BatchedWorld:
         check(self.L.rsb_get_solver_iterations(self.handle, _hp(f), RSB_HOST), "rsb_get_solver_iterations")
         return f
 
+    # -- frames: kinematics, Jacobians and external wrenches of every env in one call (rsb_frames.hip) ------------------
+    def get_field(self, field):
+        """A whole state field (RSB_F_GC / GV / PTARGET / DTARGET / TAU_FF / GENERALIZED_FORCE) as a host array [N, dim]."""
+        dim = self.nq if int(field) in (_capi.RSB_F_GC, _capi.RSB_F_PTARGET) else self.nv
+        out = np.empty((self.N, dim), np.float32)
+        check(self.L.rsb_get_field(self.handle, int(field), _hp(out), RSB_HOST), "rsb_get_field")
+        return out
+
+    def _frames(self, frames):
+        """frames: a list of (body, offset) pairs, body indices or link names -> (ctypes array of rsb_frame, count)"""
+        if isinstance(frames, (str, int, np.integer)) or (isinstance(frames, tuple) and len(frames) == 2 and np.ndim(frames[1]) == 1):
+            frames = [frames]
+        arr = (_capi.Frame * max(1, len(frames)))()
+        for k, f in enumerate(frames):
+            body, off = f if isinstance(f, (tuple, list)) else (f, (0.0, 0.0, 0.0))
+            if isinstance(body, str):
+                name, body = body, self.model.body_index(body)
+                if body < 0:
+                    raise ValueError(f"no such link: {name}")
+            arr[k].body = int(body)
+            arr[k].offset[:] = [float(x) for x in off]
+        return arr, len(frames)
+
+    @staticmethod
+    def _is_torch(x):      # a torch tensor travels as its device pointer, anything else as a host array (as VecEnv does)
+        return hasattr(x, "data_ptr") and hasattr(x, "is_cuda")
+
+    def _frame_outputs(self, names, want, shapes, out, what):
+        """-> (space, [pointer or None per name], {name: array / tensor}).  out: {name: torch CUDA tensor} (RSB_DEVICE, no synchronisation, results
+        in the caller's tensors) or {name: float32 array} (RSB_HOST); None: fresh host arrays for the outputs asked for."""
+        if out is None:
+            out = {n: np.empty(shapes[n], np.float32) for n in names if want[n]}
+        if not out:
+            raise ValueError(f"{what}: no output asked for")
+        if set(out) - set(names):
+            raise ValueError(f"{what}: unknown outputs {sorted(set(out) - set(names))}")
+        torch_like = [self._is_torch(v) for v in out.values()]
+        if any(torch_like) != all(torch_like):
+            raise ValueError(f"{what}: outputs must be all torch tensors or all numpy arrays")
+        ptrs = []
+        for n in names:
+            v = out.get(n)
+            if v is None:
+                ptrs.append(None)
+            elif torch_like[0]:
+                if not (v.is_cuda and v.is_contiguous() and str(v.dtype) == "torch.float32" and v.numel() == int(np.prod(shapes[n])) and v.device.index == self.device):
+                    raise ValueError(f"{what}: {n} must be a contiguous float32 CUDA tensor of {int(np.prod(shapes[n]))} elements on cuda:{self.device}")
+                ptrs.append(C.c_void_p(v.data_ptr()))
+            else:
+                if not (isinstance(v, np.ndarray) and v.dtype == np.float32 and v.flags.c_contiguous and v.size == int(np.prod(shapes[n]))):
+                    raise ValueError(f"{what}: {n} must be a C-contiguous float32 array of {int(np.prod(shapes[n]))} elements")
+                ptrs.append(_hp(v))
+        return (RSB_DEVICE if torch_like[0] else RSB_HOST), ptrs, out
+
+    def frame_kinematics(self, frames, pos=True, rot=False, lin_vel=False, ang_vel=False, out=None):
+        """ArticulatedSystem::getFramePosition / getFrameOrientation / getFrameVelocity / getFrameAngularVelocity (and getPosition / getVelocity of a
+        point of a body) of every env at once -> {"pos": [N, F, 3], "rot": [N, F, 3, 3] (world <- body), "lin_vel": [N, F, 3], "ang_vel": [N, F, 3]},
+        world frame, the outputs asked for only.  frames: (body, offset) pairs, body indices or link names.  out: see _frame_outputs."""
+        arr, n = self._frames(frames)
+        names = ("pos", "rot", "lin_vel", "ang_vel")
+        shapes = {"pos": (self.N, n, 3), "rot": (self.N, n, 3, 3), "lin_vel": (self.N, n, 3), "ang_vel": (self.N, n, 3)}
+        space, ptrs, out = self._frame_outputs(names, dict(pos=pos, rot=rot, lin_vel=lin_vel, ang_vel=ang_vel), shapes, out, "frame_kinematics")
+        check(self.L.rsb_get_frame_kinematics(self.handle, arr, n, *ptrs, space), "rsb_get_frame_kinematics")
+        return out
+
+    def frame_jacobians(self, frames, lin=True, rot=False, out=None):
+        """getDenseFrameJacobian / getDenseFrameRotationalJacobian of every env at once -> {"lin": [N, F, 3, nv], "rot": [N, F, 3, nv]}:
+        lin_vel = lin @ gv, ang_vel = rot @ gv (a fixed-base model keeps its six, zero, base columns)."""
+        arr, n = self._frames(frames)
+        shapes = {"lin": (self.N, n, 3, self.nv), "rot": (self.N, n, 3, self.nv)}
+        space, ptrs, out = self._frame_outputs(("lin", "rot"), dict(lin=lin, rot=rot), shapes, out, "frame_jacobians")
+        check(self.L.rsb_get_frame_jacobians(self.handle, arr, n, *ptrs, space), "rsb_get_frame_jacobians")
+        return out
+
+    def add_external_wrench(self, frame, force=None, torque=None, mask=None):
+        """setExternalForce / setExternalTorque of every env at once: tau_ff[e] += J_lin(e)^T force[e] + J_rot(e)^T torque[e] at the current state
+        for the envs with mask[e] != 0 (None: all).  force / torque [N, 3] world frame, mask [N] uint8: numpy arrays, or torch CUDA tensors (no
+        synchronisation).  The generalized force stays in the feed-forward rows until set_generalized_force replaces it."""
+        arr, n = self._frames(frame)
+        if n != 1:
+            raise ValueError("add_external_wrench: one frame expected")
+        given = [x for x in (force, torque, mask) if x is not None]
+        torch_like = [self._is_torch(x) for x in given]
+        if given and any(torch_like) != all(torch_like):
+            raise ValueError("add_external_wrench: force, torque and mask must be all torch tensors or all numpy arrays")
+        if given and torch_like[0]:
+            for x, name, dt, cnt in ((force, "force", "torch.float32", 3 * self.N), (torque, "torque", "torch.float32", 3 * self.N), (mask, "mask", "torch.uint8", self.N)):
+                if x is not None and not (x.is_cuda and x.is_contiguous() and str(x.dtype) == dt and x.numel() == cnt and x.device.index == self.device):
+                    raise ValueError(f"add_external_wrench: {name} must be a contiguous {dt} CUDA tensor of {cnt} elements on cuda:{self.device}")
+            ptrs = [None if x is None else C.c_void_p(x.data_ptr()) for x in (force, torque, mask)]
+            space = RSB_DEVICE
+        else:
+            f, t, m = _host(force, np.float32), _host(torque, np.float32), _host(mask, np.uint8)
+            for x, name, cnt in ((f, "force", 3 * self.N), (t, "torque", 3 * self.N), (m, "mask", self.N)):
+                if x is not None and x.size != cnt:
+                    raise ValueError(f"add_external_wrench: {name} must hold {cnt} elements")
+            ptrs = [_hp(f), _hp(t), _hp(m)]
+            space = RSB_HOST
+        check(self.L.rsb_add_external_wrench(self.handle, arr, *ptrs, space), "rsb_add_external_wrench")
+
     # -- observation block for the vectorised env / RCCL gather --------------------------------------
     def obs_dim(self, n_force_slots):
         return self.L.rsb_obs_dim(self.handle, int(n_force_slots))
