@@ -259,6 +259,27 @@ class BatchedWorld {
     dropStage(RSB_F_TAU_FF);      // the host mirror of the feed-forward rows is refetched on its next use
   }
 
+  /// HeightMap::getHeight / getNormal for ALL envs in one call, on the device, each env on its own terrain: xy [N,P,2] world coordinates ->
+  /// height [N,P], normal [N,P,3] (unit normal of the triangle under the point; either may be null).  Coordinates outside the map are clamped to it;
+  /// a ground plane gives its height and (0, 0, 1).  Host buffers.
+  void getTerrainHeights(const float* xy, int nPoints, float* height, float* normal) {
+    std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
+    RSB_CHECK(rsb_get_terrain_height(world_, xy, nPoints, height, normal, RSB_HOST));
+  }
+  /// The height scan of an exteroceptive observation for all envs: out[e * rowStride + f * P + k] = p_z - h(p_xy + M pattern[k]), p the world position
+  /// of frame f at the current state (staged view rows are uploaded first), pattern [P,2] with P <= RSB_MAX_SCAN_POINTS; yawAligned: M rotates the
+  /// pattern about z by the frame's heading, else M = identity.  rowStride in floats, 0 = F * P; a larger one leaves the other columns of a row alone.
+  void heightScan(const std::vector<rsb_frame>& frames, const float* pattern, int nPoints, bool yawAligned, float* out, long long rowStride = 0) {
+    std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
+    RSB_CHECK(rsb_height_scan(world_, frames.data(), (int)frames.size(), pattern, nPoints, yawAligned ? RSB_SCAN_YAW : RSB_SCAN_WORLD, out, rowStride, RSB_HOST));
+  }
+  /// World::rayTest against the terrain (not against bodies) for all envs: origins, directions [N,R,3] world frame, directions of any length ->
+  /// dist [N,R] in metres, -1 for a miss within maxDist (rsb_ray_test in rsb.h: side walls, degenerate rays).  Host buffers.
+  void rayTest(const float* origins, const float* directions, int nRays, float maxDist, float* dist) {
+    std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
+    RSB_CHECK(rsb_ray_test(world_, origins, directions, nRays, maxDist, dist, RSB_HOST));
+  }
+
   // batched, caller-owned host buffers (row-major [N, dim] float32, the raisimGymTorch matrix layout)
   void setState(const float* gc, const float* gv) {
     std::lock_guard<std::recursive_mutex> lk(mu_);

@@ -31,6 +31,9 @@
  *                                       <- ArticulatedSystem::getFramePosition/getFrameOrientation/getFrameVelocity/
  *                                          getFrameAngularVelocity/getDenseFrameJacobian/getDenseFrameRotationalJacobian/
  *                                          setExternalForce/setExternalTorque, for all envs in one call
+ *   rsb_get_terrain_height / rsb_height_scan / rsb_ray_test
+ *                                       <- HeightMap::getHeight / getNormal, World::rayTest (against the terrain), for all envs
+ *                                          in one call                                (HeightMap.hpp, World.hpp, absent)
  *   rsb_gather_obs                      <- (new) the (q, u, contact-force) observation block that
  *                                          VectorizedEnvironment::observe() is built from
  *   rsb_env_observe_normalized / rsb_env_get_obs_stats / rsb_env_set_obs_stats
@@ -281,6 +284,31 @@ int rsb_get_frame_jacobians(rsb_world* w, const rsb_frame* frames, int n_frames,
  * It stays in RSB_F_TAU_FF until rsb_set_generalized_force replaces it (upstream clears external forces after every integrate()). */
 int rsb_add_external_wrench(rsb_world* w, const rsb_frame* frame, const float* force, const float* torque,
                             const uint8_t* mask, int space);
+
+/* Terrain queries of ALL envs in one call [RECALL upstream's per-object HeightMap::getHeight / getNormal and World::rayTest, called per env on the
+ * host]: HIP kernels on the world's stream, like the frame queries above; the RSB_DEVICE forms do not synchronise, the RSB_HOST forms stage through
+ * the same device buffer.  They work on a ground plane and on a height map; with per-env maps (rsb_set_heightmaps) every env reads its own map.  The
+ * surface is the collider's: each grid cell split along its (ix, iy)-(ix+1, iy+1) diagonal, coordinates outside the footprint clamped to it.
+ *
+ * rsb_get_terrain_height: xy [N,P,2] world coordinates in `space` -> height [N,P], normal [N,P,3] (the unit normal of the triangle under the point);
+ * either output may be NULL, not both.  Ground plane: ground_z and (0, 0, 1). */
+int rsb_get_terrain_height(rsb_world* w, const float* xy, int n_points, float* height, float* normal, int space);
+/* The height scan of an exteroceptive observation: for every env, frame f and pattern point k
+ *   out[e * row_stride + f * P + k] = p_z - h(p_xy + M pattern[k]),
+ * p the frame's world position at the resident state (frames as in rsb_get_frame_kinematics, a HOST array), pattern [P,2] in `space`,
+ * P = n_points <= RSB_MAX_SCAN_POINTS.  mode RSB_SCAN_WORLD: M = identity; RSB_SCAN_YAW: M = the rotation about z by the frame's heading,
+ * (c, s) = (R[0], R[3]) / hypot(R[0], R[3]) of the body's rotation R ((1, 0) where the hypot is below 1e-6: the body's x axis is vertical).
+ * row_stride, in floats: 0 = F * P (a dense [N,F,P] output); larger values write the scan into columns [0, F * P) of rows of that pitch - pass
+ * a pointer into a wider observation tensor - and touch no other column; smaller non-zero values are RSB_E_INVALID. */
+int rsb_height_scan(rsb_world* w, const rsb_frame* frames, int n_frames, const float* pattern, int n_points, int mode,
+                    float* out, long long row_stride, int space);
+/* Rays against the terrain (not against bodies): origins, directions [N,R,3] world coordinates in `space` -> dist [N,R] in metres along the
+ * normalised direction (directions need not be unit length), -1 for a miss.  With [lo, hi] the part of [0, max_dist] where the ray is over the
+ * map's footprint, a hit is the first s in [lo, hi] with z(s) <= h(x(s), y(s)), h as in rsb_get_terrain_height: an origin below the surface
+ * gives 0, a ray that enters the footprint below the surface hits the map's side wall at s = lo, a ray that never meets the footprint misses.
+ * Ground plane: the infinite plane.  A ray with a zero or non-finite direction or a non-finite origin gives -1.  max_dist must be positive and
+ * finite.  There is no normal output: feed the hit's xy to rsb_get_terrain_height. */
+int rsb_ray_test(rsb_world* w, const float* origins, const float* directions, int n_rays, float max_dist, float* dist, int space);
 
 /* obs block [N, nq+nv+3*n_force_slots] = (q, u, contact force on chosen collision primitives).
  * collision_indices: host array of n_force_slots collision-primitive indices (e.g. the feet);

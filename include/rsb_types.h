@@ -116,6 +116,13 @@ typedef enum rsb_field {
 #define RSB_MAX_FRAMES 64         /* = RSB_MAX_BODIES: "every body" is one call */
 typedef struct rsb_frame { int32_t body; float offset[3]; } rsb_frame;
 
+/* Batched terrain queries (rsb_get_terrain_height, rsb_height_scan, rsb_ray_test; rsb.h) */
+#define RSB_MAX_SCAN_POINTS 1024  /* pattern points of one rsb_height_scan call (the pattern is staged in LDS) */
+typedef enum rsb_scan_mode {
+  RSB_SCAN_WORLD = 0,             /* pattern offsets along the world's x and y */
+  RSB_SCAN_YAW = 1                /* pattern rotated about z by the frame's heading */
+} rsb_scan_mode;
+
 #define RSB_MAX_RANKS 8           /* ranks of one node (peer-mapped obs exchange, rsb.h) */
 
 #ifdef __cplusplus

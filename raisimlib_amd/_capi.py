@@ -49,6 +49,8 @@ class Frame(C.Structure):
 
 
 RSB_MAX_FRAMES = 64
+RSB_MAX_SCAN_POINTS = 1024
+RSB_SCAN_WORLD, RSB_SCAN_YAW = 0, 1
 
 
 class TerrainProperties(C.Structure):
@@ -199,6 +201,9 @@ PROTOTYPES = {
     "rsb_get_frame_kinematics": (_I, [_VP, C.POINTER(Frame), _I, _FP, _FP, _FP, _FP, _I]),
     "rsb_get_frame_jacobians": (_I, [_VP, C.POINTER(Frame), _I, _FP, _FP, _I]),
     "rsb_add_external_wrench": (_I, [_VP, C.POINTER(Frame), _FP, _FP, _FP, _I]),
+    "rsb_get_terrain_height": (_I, [_VP, _FP, _I, _FP, _FP, _I]),
+    "rsb_height_scan": (_I, [_VP, C.POINTER(Frame), _I, _FP, _I, _I, _FP, C.c_longlong, _I]),
+    "rsb_ray_test": (_I, [_VP, _FP, _FP, _I, C.c_float, _FP, _I]),
     "rsb_obs_dim": (_I, [_VP, _I]),
     "rsb_gather_obs": (_I, [_VP, _FP, _FP, _I, _I]),
     "rsb_reset_terminated": (_I, [_VP, _FP, _I, _FP, _FP, _I, _FP, _I]),

@@ -129,7 +129,7 @@ struct rsb_world {
   // normaliser and an MLP stage read, and the fold's scratch: block partials and batch moments (obs_part_batches batches of them)
   double* d_obs_stats = nullptr; float* d_obs_view = nullptr; double* d_obs_part = nullptr;
   int obs_part_batches = 0;
-  // batched frame queries (rsb_frames.hip): staging of the RSB_HOST forms' outputs / wrench inputs, grown on demand
+  // batched frame and terrain queries (rsb_frames.hip, rsb_terrain_query.hip): staging of the RSB_HOST forms' inputs / outputs, grown on demand
   float* d_frames_io = nullptr; size_t frames_io_cap = 0;
   std::vector<hipEvent_t> ring0, ring1;   // event pairs around the most recent step-kernel launches (rsb_enable_timing(w, n))
   size_t ring_next = 0, ring_count = 0;
@@ -214,6 +214,7 @@ int rk4_integrate(rsb_world* w, int nsub);                        // rsb_rk4.hip
 int obs_stats_init(rsb_world* w);                                 // rsb_obstats.hip: the observation statistics at their initial state (rsb_env_configure, once)
 void obs_stats_free(rsb_world* w);                                // rsb_obstats.hip (rsb_destroy)
 void frames_free(rsb_world* w);                                   // rsb_frames.hip (rsb_destroy)
+int staging(rsb_world* w, size_t floats);                         // rsb_frames.hip: d_frames_io, the staging buffer of the RSB_HOST forms of the frame and terrain queries, at least `floats` long
 // rsb_pipeline.hip
 hipStream_t stream_of(rsb_world* w);                              // the world's stream for any use other than a pipelined launch (joins first)
 int pipe_join(rsb_world* w);

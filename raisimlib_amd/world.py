@@ -542,6 +542,101 @@ class BatchedWorld:
             space = RSB_HOST
         check(self.L.rsb_add_external_wrench(self.handle, arr, *ptrs, space), "rsb_add_external_wrench")
 
+    # -- terrain: heights, height scans and ray tests of every env in one call (rsb_terrain_query.hip) -------------------
+    def _terrain_io(self, what, inputs, out_shapes, out):
+        """inputs {name: (value, shape)}, out_shapes {name: shape}, out {name: array / tensor or None} -> (space, input pointers, output pointers,
+        outputs).  The conventions of _frame_outputs: torch CUDA tensors travel as device pointers (RSB_DEVICE, no synchronisation), anything else
+        as float32 host arrays (RSB_HOST); inputs and outputs must agree."""
+        given = [v for v, _ in inputs.values()] + [v for v in out.values() if v is not None]
+        torch_like = [self._is_torch(v) for v in given]
+        if any(torch_like) != all(torch_like):
+            raise ValueError(f"{what}: inputs and outputs must be all torch tensors or all numpy arrays")
+        dev = torch_like[0]
+
+        def tensor_ptr(n, v, shape):
+            cnt = int(np.prod(shape))
+            if not (v.is_cuda and v.is_contiguous() and str(v.dtype) == "torch.float32" and v.numel() == cnt and v.device.index == self.device):
+                raise ValueError(f"{what}: {n} must be a contiguous float32 CUDA tensor of {cnt} elements on cuda:{self.device}")
+            return C.c_void_p(v.data_ptr())
+        keep, in_ptrs, out_ptrs, res = [], [], [], {}
+        for n, (v, shape) in inputs.items():
+            if dev:
+                in_ptrs.append(tensor_ptr(n, v, shape))
+            else:
+                a = _host(v, np.float32)
+                if a.size != int(np.prod(shape)):
+                    raise ValueError(f"{what}: {n} must hold {int(np.prod(shape))} elements")
+                keep.append(a)
+                in_ptrs.append(_hp(a))
+        for n, shape in out_shapes.items():
+            v = out.get(n)
+            if v is None:
+                if dev:
+                    raise ValueError(f"{what}: with torch inputs pass the outputs as torch tensors (out=)")
+                v = np.empty(shape, np.float32)
+            if dev:
+                out_ptrs.append(tensor_ptr(n, v, shape))
+            else:
+                if not (isinstance(v, np.ndarray) and v.dtype == np.float32 and v.flags.c_contiguous and v.size == int(np.prod(shape))):
+                    raise ValueError(f"{what}: {n} must be a C-contiguous float32 array of {int(np.prod(shape))} elements")
+                out_ptrs.append(_hp(v))
+            res[n] = v
+        return (RSB_DEVICE if dev else RSB_HOST), in_ptrs, out_ptrs, res, keep
+
+    def terrain_height(self, points, normal=False, out=None):
+        """HeightMap::getHeight (and getNormal) of every env at once: points [N, P, 2] world xy -> height [N, P], or (height, normal [N, P, 3]) with
+        normal=True; coordinates outside the map are clamped to it, a ground plane gives its height and (0, 0, 1).  points a numpy array: host
+        arrays back; a float32 torch CUDA tensor: out = {"height": tensor, "normal": tensor} (either one alone is enough), no synchronisation."""
+        P = int(np.prod(points.shape)) // (2 * self.N)
+        out = dict(out or {})
+        if set(out) - {"height", "normal"}:
+            raise ValueError(f"terrain_height: unknown outputs {sorted(set(out) - {'height', 'normal'})}")
+        shapes = {"height": (self.N, P), "normal": (self.N, P, 3)}
+        want = [n for n in shapes if n in out or (not self._is_torch(points) and (n == "height" or normal))]
+        space, ins, outs, res, _keep = self._terrain_io("terrain_height", {"points": (points, (self.N, P, 2))}, {n: shapes[n] for n in want}, out)
+        ptr = dict(zip(want, outs))
+        check(self.L.rsb_get_terrain_height(self.handle, ins[0], P, ptr.get("height"), ptr.get("normal"), space), "rsb_get_terrain_height")
+        if "normal" in res and "height" in res:
+            return res["height"], res["normal"]
+        return res["height"] if "height" in res else res["normal"]
+
+    def height_scan(self, frames, pattern, yaw_aligned=True, out=None, row_stride=0):
+        """Height of each frame above the terrain under a pattern of points around it: [N, F, P], out[e, f, k] = p_z - h(p_xy + M pattern[k]), p the
+        frame's world position, pattern [P, 2]; yaw_aligned: M rotates the pattern about z by the frame's heading, else M = identity.  frames as in
+        frame_kinematics.  row_stride (floats, 0 = F * P): with a larger value `out` is the first scan column of a wider [N, row_stride] buffer -
+        a torch view such as obs[:, k:] (only its data pointer is used) or a numpy array of N * row_stride floats - whose other columns are left alone."""
+        arr, F = self._frames(frames)
+        P = int(np.prod(pattern.shape)) // 2
+        width = F * P
+        stride = int(row_stride) or width
+        mode = _capi.RSB_SCAN_YAW if yaw_aligned else _capi.RSB_SCAN_WORLD
+        if stride == width:
+            space, ins, outs, res, _keep = self._terrain_io("height_scan", {"pattern": (pattern, (P, 2))}, {"out": (self.N, F, P)}, {"out": out})
+            check(self.L.rsb_height_scan(self.handle, arr, F, ins[0], P, mode, outs[0], 0, space), "rsb_height_scan")
+            return res["out"]
+        if out is None or self._is_torch(out) != self._is_torch(pattern):
+            raise ValueError("height_scan: a row_stride needs `out`, of the pattern's kind (torch tensor or numpy array)")
+        space, ins, _, _, _keep = self._terrain_io("height_scan", {"pattern": (pattern, (P, 2))}, {}, {})
+        if space == RSB_DEVICE:
+            if not (out.is_cuda and str(out.dtype) == "torch.float32" and out.device.index == self.device):
+                raise ValueError(f"height_scan: out must be a float32 CUDA tensor on cuda:{self.device}")
+            optr = C.c_void_p(out.data_ptr())
+        else:
+            if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and out.size >= (self.N - 1) * stride + width):
+                raise ValueError("height_scan: out must be a C-contiguous float32 array that holds N rows of row_stride floats")
+            optr = _hp(out)
+        check(self.L.rsb_height_scan(self.handle, arr, F, ins[0], P, mode, optr, stride, space), "rsb_height_scan")
+        return out
+
+    def ray_test(self, origins, directions, max_dist, out=None):
+        """World::rayTest against the terrain for every env at once: origins, directions [N, R, 3] world frame (directions of any length) ->
+        dist [N, R], metres to the first hit within max_dist, -1 for a miss (see rsb_ray_test in rsb.h for the side wall and the degenerate rays)."""
+        R = int(np.prod(origins.shape)) // (3 * self.N)
+        space, ins, outs, res, _keep = self._terrain_io("ray_test", {"origins": (origins, (self.N, R, 3)), "directions": (directions, (self.N, R, 3))},
+                                                        {"dist": (self.N, R)}, {"dist": out})
+        check(self.L.rsb_ray_test(self.handle, ins[0], ins[1], R, float(max_dist), outs[0], space), "rsb_ray_test")
+        return res["dist"]
+
     # -- observation block for the vectorised env / RCCL gather --------------------------------------
     def obs_dim(self, n_force_slots):
         return self.L.rsb_obs_dim(self.handle, int(n_force_slots))
