@@ -293,18 +293,14 @@ int pipe_recover(rsb_world* w, int code) {
   w->world_time -= w->pipe_time_logged;
   std::vector<rsb_world::PipeLog> log;
   log.swap(w->pipe_log);
-  const uint8_t* keep_done = w->d_done_out;
   for (auto& e : log) {
     if (e.closed) {
       st = closed_loop_lockstep(w, e.K, e.is_linear ? nullptr : e.is_mlp ? launch_mlp_stage : e.launch, e.is_linear ? (void*)&e.lin : e.is_mlp ? (void*)&e.mlp : e.user, e.pass_global0);
     } else {
-      w->fuse = e.f; w->fuse.pipeline = false;
-      w->d_done_out = e.done_out;
-      st = do_integrate(w, e.nsub);
+      st = do_integrate(w, e.nsub, e.req);
     }
     if (st != RSB_OK) break;
   }
-  w->d_done_out = const_cast<uint8_t*>(keep_done);
   w->integrate1_valid = false;
   return st;
 }
@@ -446,15 +442,10 @@ void cl_fill_ctx(rsb_world* w, rsb_stage_ctx* c, int K, long long pass_global0) 
   c->ob_dim = 10 + 2 * (w->blob.nv - 6); c->act_dim = w->blob.nv - 6;
 }
 // one closed-loop step of the env task: actions from the world's own buffer, reward / done / next observation into the world's own buffers
-void cl_fuse(rsb_world* w, bool pipelined) {
-  rsb_world::Fuse f;
-  f.act = w->d_env_act;
-  f.have_allowed = 1; f.allowed = w->env_allowed;
-  f.do_reset = 1; f.gc0 = w->d_env_gc0; f.gv0 = w->d_env_gv0; f.rows = 1;
-  if (w->d_env_gc0_rows) { f.gc0 = w->d_env_gc0_rows; f.gv0 = w->d_env_gv0_rows; f.rows = w->N; }      // rsb_env_set_reset_states
-  f.env_task = true; f.env_reward = w->d_env_reward; f.env_ob = w->d_env_ob; f.env_done = w->d_env_done;
+StepRequest cl_request(const rsb_world* w, bool pipelined) {
+  StepRequest f = env_task_request(w, w->d_env_act, w->d_env_reward, w->d_env_ob, w->d_env_done);
   f.closed_loop = pipelined; f.pipeline = pipelined;
-  w->fuse = f;
+  return f;
 }
 
 // pass 0, step 1, pass 1, ..., step K, pass K on the world's stream; launch == nullptr: the linear stage with *user = rsb_linear_policy
@@ -470,8 +461,7 @@ int closed_loop_lockstep(rsb_world* w, int K, rsb_stage_launch_fn launch, void* 
     c.pass_first = c.pass_last = t;
     if (launch(user, &c) != 0) { rsb::set_error("rsb_closed_loop_run: the action stage's launch function failed"); return RSB_E_HIP; }
     if (t == K) break;
-    cl_fuse(w, false);
-    st = do_integrate(w, w->env_cfg.n_substeps);
+    st = do_integrate(w, w->env_cfg.n_substeps, cl_request(w, false));
     if (st != RSB_OK) return st;
   }
   w->integrate1_valid = false;
@@ -483,11 +473,11 @@ int closed_loop_resident(rsb_world* w, int K, const rsb_linear_policy* lin, cons
   hipStream_t s = stream_of(w);      // joins
   int st = RSB_OK;
   if (!w->env_ob_valid) { st = launch_env_obs(w, w->d_env_ob, s); if (st != RSB_OK) return st; }
-  cl_fuse(w, false);
-  w->fuse.res_steps = K; w->fuse.res_stage = lin ? 1 : 2; w->fuse.res_pass_global0 = pass_global0;
-  if (lin) w->fuse.res_lin = *lin;
-  if (mlp) w->fuse.res_mlp = *mlp;
-  st = do_integrate(w, w->env_cfg.n_substeps);
+  StepRequest f = cl_request(w, false);
+  f.res_steps = K; f.res_stage = lin ? 1 : 2; f.res_pass_global0 = pass_global0;
+  if (lin) f.res_lin = *lin;
+  if (mlp) f.res_mlp = *mlp;
+  st = do_integrate(w, w->env_cfg.n_substeps, f);
   w->integrate1_valid = false;
   return st;
 }
@@ -495,7 +485,7 @@ int closed_loop_resident(rsb_world* w, int K, const rsb_linear_policy* lin, cons
 // the conditions under which do_integrate launches a step of a closed-loop run on the pipeline (else it takes the world's stream - and joins, with the
 // action stage in flight: ADVICE r05).  Checked BEFORE the stage is launched; a run that fails the test stays in lock-step.
 bool closed_loop_can_pipeline(const rsb_world* w) {
-  return pipelining_allowed(w, w->peer.connected, w->launch_mask) && !(w->integ_rk4 && !w->rk4_inner);
+  return pipelining_allowed(w, w->peer.connected, nullptr) && !w->integ_rk4;      // (a run's steps carry no env mask)
 }
 
 int closed_loop_run_inner(rsb_world* w, int K, rsb_stage_launch_fn launch, void* user, const rsb_linear_policy* lin, const rsb_mlp_policy* mlp, long long pg0);
@@ -526,7 +516,7 @@ int closed_loop_run_inner(rsb_world* w, int K, rsb_stage_launch_fn launch, void*
   cl_fill_ctx(w, &c, K, pg0);
   int st = check_lpe(w, effective_lpe(w));
   if (st != RSB_OK) return st;
-  st = upload_image(w, world_layout(w));          // (do_integrate would do it - and JOIN for it, with the stage already in flight)
+  st = upload_image(w, world_layout(w), false);          // (do_integrate would do it - and JOIN for it, with the stage already in flight)
   if (st != RSB_OK) return st;
   st = pipe_prepare(w, c.blocks);
   if (st != RSB_OK) return st;
@@ -583,16 +573,13 @@ int closed_loop_run_inner(rsb_world* w, int K, rsb_stage_launch_fn launch, void*
   e.is_linear = lin != nullptr; if (lin) e.lin = *lin;
   e.is_mlp = mlp != nullptr; if (mlp) e.mlp = *mlp;
   w->pipe_log.push_back(e);
-  w->pipe_log_suppress = true;
-  for (int t = 0; t < K && st == RSB_OK; ++t) {
-    cl_fuse(w, true);
-    st = do_integrate(w, w->env_cfg.n_substeps);
+  for (int t = 0; t < K && st == RSB_OK; ++t) {      // (closed_loop requests: the run above is the log's ONE entry for them)
+    st = do_integrate(w, w->env_cfg.n_substeps, cl_request(w, true));
     if (st == RSB_OK && !w->pipe_active) {      // the step did not go to the pipeline (it joined): the stage has nobody to wait for - treat it as a failed enqueue
       rsb::set_error("rsb_closed_loop_run: a step of the run left the pipeline (profiling / debug instrumentation switched on mid-run?)");
       st = RSB_E_STATE;
     }
   }
-  w->pipe_log_suppress = false;
   if (st != RSB_OK) {
     // a step could not be enqueued: the stage would wait for it until its time-out.  Tell the device now, then join (recovers from the snapshot)
     hipLaunchKernelGGL(set_word_kernel, dim3(1), dim3(1), 0, w->stream, err_ptr(w), w->d_pipe_err_host, RSB_PIPE_ERR_INJECTED);

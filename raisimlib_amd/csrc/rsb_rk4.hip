@@ -159,16 +159,14 @@ __global__ void rk4_position_kernel(float* gc, const float* gv, const float* q0,
 
 }  // namespace
 
-int rk4_integrate(rsb_world* w, int nsub) {
+int rk4_integrate(rsb_world* w, int nsub, const StepRequest& req) {
   const size_t N = w->N, nq = w->blob.nq, nv = w->blob.nv;
-  const rsb_world::Fuse f = w->fuse;
-  if (f.ptarget_src || f.act || f.obs_out || f.do_reset || f.env_task || f.peer) {
-    w->fuse = rsb_world::Fuse();
+  if (req.fuses()) {
     rsb::set_error("RUNGE_KUTTA_4: plain integrate() calls only (rsb_integrate, rsb_integrate_masked, the World views) - the fused control step / env step run the one-evaluation schemes");
     return RSB_E_UNSUPPORTED;
   }
   hipStream_t s = stream_of(w);
-  const uint8_t* mask = w->launch_mask;
+  const uint8_t* const mask = req.mask;
   if (!w->d_rk) {
     // q0 | u0 | ka [4] | kv [4] | theta | du | h0 | tff saved | M0
     const size_t floats = N * nq + N * nv * (1 + 4 + 4 + 1 + 1 + 1 + 1) + N * nv * nv;
@@ -178,7 +176,7 @@ int rk4_integrate(rsb_world* w, int nsub) {
   float* du = theta + N * nv; float* h0 = du + N * nv; float* tff_save = h0 + N * nv; float* M0 = tff_save + N * nv;
   const int blocks = (int)((N + 63) / 64);
   // One sub-step; on ANY failure part-way through the world is put back to the state the sub-step started from (gc / gv used to be left at
-  // a stage state, d_tff at tau_eff, the launch mask set - the next integrate() then ran from corrupted inputs without a word)
+  // a stage state, d_tff at tau_eff - the next integrate() then ran from corrupted inputs without a word)
   bool have_q0 = false, tff_dirty = false;
   auto substep = [&]() -> int {
     have_q0 = false; tff_dirty = false;
@@ -206,16 +204,10 @@ int rk4_integrate(rsb_world* w, int nsub) {
     tff_dirty = true;       // (the combine kernel overwrites d_tff with tau_eff)
     hipLaunchKernelGGL(rk4_combine_kernel, dim3(blocks), dim3(64), 0, s, c);
     HIP_TRY(hipGetLastError());
-    // the contact step: the one-evaluation kernel in force mode, without the effort clip (tau_eff carries inertial terms), semi-implicit positions
-    const int mode = w->control_mode;
-    const double theta_keep = w->integ_theta;
-    w->control_mode = RSB_FORCE_AND_TORQUE; w->rk4_inner = true; w->integ_theta = 1.0; w->image_dirty = true;
-    w->launch_mask = mask;
-    const bool tz = w->tff_zero;
-    w->tff_zero = false;          // (tau_eff lives in d_tff for this launch)
-    int st = do_integrate(w, 1);
-    w->tff_zero = tz;
-    w->control_mode = mode; w->rk4_inner = false; w->integ_theta = theta_keep; w->image_dirty = true;
+    // the contact step: the one-evaluation kernel in force mode, without the effort clip (tau_eff carries inertial terms), semi-implicit positions - by the request's flag
+    StepRequest contact;
+    contact.rk4_contact = true; contact.mask = mask;
+    int st = do_integrate(w, 1, contact);
     if (st != RSB_OK) return st;
     hipLaunchKernelGGL(rk4_position_kernel, dim3(blocks), dim3(64), 0, s, w->d_gc, w->d_gv, q0, u0, theta, du, mask, w->d_model, (int)N, (int)nq, (int)nv, (float)w->dt);
     HIP_TRY(hipGetLastError());
@@ -235,7 +227,6 @@ int rk4_integrate(rsb_world* w, int nsub) {
     (void)hipGetLastError();
     rsb::set_error(msg + " (RUNGE_KUTTA_4: the sub-step was rolled back)");
   }
-  w->launch_mask = nullptr;
   w->integrate1_valid = false; w->env_ob_valid = false;
   return status;
 }

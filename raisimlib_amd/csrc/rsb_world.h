@@ -1,7 +1,10 @@
 // rsb_world.h — the batched world's host-side state and the helpers its translation units share (not installed):
 //   rsb_world.hip     the core of the C-ABI (include/rsb.h): creation, setters, state transfer, the step launch (do_integrate), queries, env task
+//   rsb_rk4.hip       IntegrationScheme::RUNGE_KUTTA_4, host-driven over the query kernels and one contact step of the step kernel
 //   rsb_pipeline.hip  pipelined control steps: private streams, probes, gates, join + fault recovery, the closed-loop run (include/rsb_pipeline.h)
 //   rsb_comm.hip      multi-GPU: the RCCL obs all-gather and the peer-mapped obs exchange
+// rsb_world holds what the world IS (configuration, buffers, the pipeline's bookkeeping); what ONE launch of the step kernel should do beyond that is a
+// rsbw::StepRequest handed to do_integrate: no caller writes a launch's wishes into the world, so a refused launch has nothing to leave behind.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -28,6 +31,24 @@ using rsbk::StepArgs;
     }                                                                                           \
   } while (0)
 
+namespace rsbw {
+// what one launch of the step kernel is asked to do beyond the world's configuration (do_integrate); default-constructed: a plain integrate()
+struct StepRequest {
+  bool peer = false; const float* act = nullptr; const float* ptarget_src = nullptr; float* obs_out = nullptr; const int32_t* obs_idx = nullptr; int obs_slots = 0;
+  int do_reset = 0, have_allowed = 0; unsigned long long allowed = 0; const float *gc0 = nullptr, *gv0 = nullptr; int rows = 1;
+  float* env_reward = nullptr; float* env_ob = nullptr; bool env_task = false;
+  bool pipeline = false;              // may go to the pipeline (rsb_set_step_pipelining); false: never, as in a fault's replay
+  bool closed_loop = false;           // a pipelined step of rsb_closed_loop_run: waits for the action stage's word, and the RUN is logged for a replay, not its steps
+  bool rk4_contact = false;           // RUNGE_KUTTA_4's own contact step (rsb_rk4.hip): force mode without the effort clip, theta = 1, d_tff read whatever tff_zero says
+  const uint8_t* mask = nullptr;      // [N] device: envs with a zero keep their state (rsb_integrate_masked, the views)
+  bool redirect_done = false; uint8_t* done_out = nullptr;      // redirect_done: the done flags go to done_out ([N], or [K, N] of a resident launch; NULL: nowhere), not to the world's rsb_set_done_output buffer
+  // resident launch (rsb_set_step_residency): K control steps in this ONE launch; stage 0 = open loop (targets from a bank), 1 = linear policy, 2 = actor network
+  int res_steps = 0, res_stage = 0; const float* res_targets = nullptr; int res_period = 0; long long res_first = 0, res_obs_stride = 0, res_done_stride = 0, res_pass_global0 = 0;
+  rsb_linear_policy res_lin{}; rsb_mlp_policy res_mlp{};
+  bool fuses() const { return ptarget_src || act || obs_out || do_reset || env_task || peer; }      // anything but a plain (masked) integrate()
+};
+}  // namespace rsbw
+
 struct rsb_world {
   rsb_model_blob blob;
   int N = 0, device = 0;
@@ -48,6 +69,7 @@ struct rsb_world {
   std::vector<double> col_mu, col_rest, col_rthr;   // per-primitive overrides, < 0 = the world's default
   bool image_dirty = true;
   LdsLayout image_layout{};           // the layout d_image was built for (upload_image rebuilds it for a launch of another one)
+  bool image_rk4_contact = false;     // ... and whether for RUNGE_KUTTA_4's contact step (no gains, no effort clip)
   // self-collision (rsb_set_self_collision): candidate primitive pairs i < j in enumeration order, body pairs the caller
   // excluded (rsb_ignore_collision_between), per-pair material overrides (< 0 = the world's default)
   bool self_collision = true;
@@ -61,8 +83,7 @@ struct rsb_world {
   float* d_warm = nullptr;   // [N, kWarmRow] contact-solver warm state (StepArgs::warm: one record per contact of the last integrate())
   bool warm_start = true;
   uint8_t* d_done_out = nullptr;        // caller-owned device buffer (rsb_set_done_output): done flags of the fused control step
-  const uint8_t* launch_mask = nullptr; // env mask of the next launch only (rsb_integrate_masked)
-  uint8_t* d_launch_mask = nullptr;     // staging for host masks
+  uint8_t* d_launch_mask = nullptr;     // staging for host masks (rsb_integrate_masked)
   uint8_t* d_view_masks = nullptr;      // [n_launches][N] launch masks of rsb_view_exchange
   size_t view_masks_cap = 0;
   void* comm = nullptr;                 // ncclComm_t (rsb_comm_init)
@@ -85,7 +106,7 @@ struct rsb_world {
   int hm_contacts = 1; double hm_second_cos = 0.70710678118654752;                                        // rsb_set_heightmap_contacts
   bool hm_capsule = false; int32_t* d_cap = nullptr; int n_cap = 0;                                       // rsb_set_capsule_contacts: [n_cap][2] end primitives of the model's capsules / cylinders, (first corner, -1) of its boxes
   int slip_rule = 0;                                                                       // rsb_set_slip_rule (RSB_SLIP_ENERGY / RSB_SLIP_COULOMB)
-  bool integ_rk4 = false, rk4_inner = false;                                                // IntegrationScheme::RUNGE_KUTTA_4 (rsb_rk4.hip); rk4_inner: the scheme's own contact step is being launched
+  bool integ_rk4 = false;                                                                  // IntegrationScheme::RUNGE_KUTTA_4 (rsb_rk4.hip)
   float* d_rk = nullptr;                                                                   // its scratch
   double integ_theta = 1.0;                                                                // rsb_set_integration_scheme
   // peer-mapped obs exchange (rsb_obs_peer_*).  ONE allocation per rank, the same layout on every rank:
@@ -112,13 +133,6 @@ struct rsb_world {
   bool env_ob_valid = false;            // d_env_ob holds the env-task observation of the CURRENT state (left there by the last env-task step; any other state change clears it)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timing = false;
-  // epilogue / prologue fused into the next launch by rsb_control_step (consumed by do_integrate)
-  struct Fuse { bool peer = false; const float* act = nullptr; const float* ptarget_src = nullptr; float* obs_out = nullptr; const int32_t* obs_idx = nullptr; int obs_slots = 0;
-                int do_reset = 0, have_allowed = 0; unsigned long long allowed = 0; const float *gc0 = nullptr, *gv0 = nullptr; int rows = 1;
-                float* env_reward = nullptr; float* env_ob = nullptr; uint8_t* env_done = nullptr; bool env_task = false; bool pipeline = false; bool closed_loop = false;
-                // resident launch (rsb_set_step_residency): K control steps in this ONE launch; stage 0 = open loop (targets from a bank), 1 = linear policy, 2 = actor network
-                int res_steps = 0, res_stage = 0; const float* res_targets = nullptr; int res_period = 0; long long res_first = 0, res_obs_stride = 0, res_done_stride = 0, res_pass_global0 = 0;
-                uint8_t* res_done = nullptr; rsb_linear_policy res_lin{}; rsb_mlp_policy res_mlp{}; } fuse;
   // device-resident vectorised env (rsb_env_*)
   bool env_ready = false;
   rsb_env_config env_cfg{};
@@ -148,7 +162,6 @@ struct rsb_world {
   unsigned long long* d_pipe_started = nullptr;
   int* d_pipe_prog = nullptr;                            // step_prog [pipe_blocks * pipe_stride] | act_prog [pipe_blocks * pipe_stride]: block b's words at b * pipe_stride
   int pipe_stride = 64;                                  // ints between the words of consecutive blocks (256 B: spread over the memory channels; RSB_PIPE_WORD_STRIDE)
-  hipStream_t launch_stream = nullptr;                   // stream of the step launch being enqueued (do_integrate)
   hipStream_t pipe_last = nullptr;                       // private stream of the most recent pipelined launch
   hipEvent_t pipe_dep = nullptr, pipe_pub = nullptr;     // rsb_step_pipeline_wait_event: the next pipelined launch waits for it; event of rsb_step_pipeline_publish
   long long pipe_launches = 0, pipe_joins = 0;
@@ -164,13 +177,12 @@ struct rsb_world {
   float* d_snap = nullptr; size_t snap_cap = 0;          // gc | gv | warm records at the last fork (what a faulted pipeline is replayed from)
   struct PipeLog {                                       // one call since the last fork: a control step (open loop) or a whole closed-loop run
     bool closed = false;
-    Fuse f; int nsub = 0; uint8_t* done_out = nullptr;
+    rsbw::StepRequest req; int nsub = 0;                 // (req: not pipelined, its done output resolved when it was logged)
     int K = 0; rsb_stage_launch_fn launch = nullptr; void* user = nullptr; long long pass_global0 = 0;
     bool is_linear = false; rsb_linear_policy lin{};
     bool is_mlp = false; rsb_mlp_policy mlp{};
   };
   std::vector<PipeLog> pipe_log;
-  bool pipe_log_suppress = false;                        // the steps of a closed-loop run are logged as ONE entry
   double pipe_time_logged = 0.0;                         // world time the logged calls advanced (taken back before a replay)
   hipStream_t pipe_stage_stream = nullptr;               // the action stage's stream (overlaps with both step streams)
   bool pipe_stage_overlap = true;
@@ -196,21 +208,22 @@ namespace rsbw {
 // a kernel class: the template arguments of rsbk::rsb_step_kernel a launch runs with (an entry of step_launch.h's RSB_STEP_INSTANCES; prof: its profiling twin)
 struct StepClass { int lpe, kmax, cl, ml, prof = 0; };
 // what a launch asks of the class beyond the world's configuration: the peer exchange in its epilogue, a pipelined twin, a resident launch
-// (res_stage 0 open loop, 1 linear policy, 2 actor network of greatest width mlp_width; -1 not resident)
-struct LaunchKind { bool peer = false, pipelined = false; int res_stage = -1, mlp_width = 0; };
+// (res_stage 0 open loop, 1 linear policy, 2 actor network of greatest width mlp_width; -1 not resident), RUNGE_KUTTA_4's contact step (theta = 1)
+struct LaunchKind { bool peer = false, pipelined = false, rk4_contact = false; int res_stage = -1, mlp_width = 0; };
 int choose_step_class(const rsb_world* w, const LaunchKind& k, StepClass* out);   // RSB_OK, or RSB_E_UNSUPPORTED with the reason in the error string
 bool instrumented(const rsb_world* w);                          // profiling / debug instrumentation is on: launches run the profiling twin
 bool pipelining_allowed(const rsb_world* w, bool peer, const uint8_t* mask);   // what a pipelined step launch needs of the world (do_integrate, closed loop)
 LdsLayout world_layout(const rsb_world* w);                     // the step kernel's LDS layout for this world as configured
-int do_integrate(rsb_world* w, int nsub);
-int upload_image(rsb_world* w, const LdsLayout& L);            // the step kernel's per-block tables, when a setter dirtied them or L is new (joins)
+int do_integrate(rsb_world* w, int nsub, const StepRequest& req);      // EVERY launch of the step kernel
+int upload_image(rsb_world* w, const LdsLayout& L, bool rk4_contact);   // the step kernel's per-block tables, when a setter dirtied them or (L, rk4_contact) is new (joins)
 int effective_lpe(const rsb_world* w);
 int check_lpe(const rsb_world* w, int lpe);
 int copy_in(rsb_world* w, float* dst, const float* src, size_t n, int space);
 int copy_out(rsb_world* w, void* dst, const void* src, size_t bytes, int space);
-int launch_env_obs(rsb_world* w, float* dst, hipStream_t s);
+int launch_env_obs(rsb_world* w, float* dst, hipStream_t s);      // the stand-alone env-task observation of the current state
+StepRequest env_task_request(const rsb_world* w, const float* act, float* reward, float* ob, uint8_t* done);   // one step of the env task (rsb_env_step, closed loop)
 int launch_dynamics_query(rsb_world* w, hipStream_t s);           // M, h and M^-1 of the current state into d_M / d_h / d_Minv (the query kernels)
-int rk4_integrate(rsb_world* w, int nsub);                        // rsb_rk4.hip     // the stand-alone env-task observation of the current state
+int rk4_integrate(rsb_world* w, int nsub, const StepRequest& req);   // rsb_rk4.hip
 int obs_stats_init(rsb_world* w);                                 // rsb_obstats.hip: the observation statistics at their initial state (rsb_env_configure, once)
 void obs_stats_free(rsb_world* w);                                // rsb_obstats.hip (rsb_destroy)
 void frames_free(rsb_world* w);                                   // rsb_frames.hip (rsb_destroy)

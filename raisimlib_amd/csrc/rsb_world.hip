@@ -375,7 +375,7 @@ int choose_step_class(const rsb_world* w, const LaunchKind& k, StepClass* out) {
   const bool resident = k.res_stage >= 0;
   const bool peer = resident ? w->peer.connected : k.peer;
   const bool hm2 = (w->hm_contacts >= 2 || (w->hm_capsule && w->n_cap > 0)) && w->terrain_type == 1;   // more than one contact per primitive against a height map
-  const bool th = w->integ_theta != 1.0, coul = w->slip_rule == RSB_SLIP_COULOMB;
+  const bool th = w->integ_theta != 1.0 && !k.rk4_contact, coul = w->slip_rule == RSB_SLIP_COULOMB;
   const int needs = (b.fixed_base ? 1 : 0) | (peer ? 2 : 0) | (hm2 ? 4 : 0) | (th ? 8 : 0) | (coul ? 32 : 0);
   const int mlv = b.depth - 1;
   StepClass c{effective_lpe(w), kcap_of(b, w->kmax), needs, mlv <= 4 ? 4 : mlv <= 12 ? 12 : mlv <= 16 ? 16 : 0, instrumented(w) ? 1 : 0};
@@ -419,8 +419,9 @@ LdsLayout world_layout(const rsb_world* w) { return make_layout(w->blob, kcap_of
 
 // The per-block tables of the step kernel exactly as they sit in LDS (LdsLayout::t_*): the kernel copies this image with
 // float4 loads instead of staging ten tables one latency-bound loop at a time.  Rebuilt when a setter changes what it bakes
-// in: PD gains, control mode, contact materials - and for a launch of another layout (the model table's pitch follows the contact capacity: make_layout).
-std::vector<float> build_lds_image(const rsb_world* w, const LdsLayout& L) {
+// in: PD gains, control mode, contact materials - and for a launch of another layout (the model table's pitch follows the contact capacity: make_layout)
+// or of the other kind: RUNGE_KUTTA_4's contact step (rk4_contact) runs in force mode, so without the gains, and without the effort clip.
+std::vector<float> build_lds_image(const rsb_world* w, const LdsLayout& L, bool rk4_contact) {
   const rsb_model_blob& b = w->blob;
   auto dm = std::make_unique<DevModel>();
   build_dev_model(b, dm.get());
@@ -428,8 +429,8 @@ std::vector<float> build_lds_image(const rsb_world* w, const LdsLayout& L) {
   auto put_i = [&](int off, int v) { std::memcpy(&img[off], &v, sizeof(int)); };
   for (int i = 0; i < b.nb; ++i) {
     for (int c = 0; c < rsbk::kModelSlot; ++c) img[L.t_model + i * L.model_pitch + c] = dm->bodyf[i][c];
-    if (w->rk4_inner) img[L.t_model + i * L.model_pitch + 28] = 0.f;      // (RUNGE_KUTTA_4's contact step: its generalized force carries inertial terms, the effort clip was applied in the stages)
-    const bool pd = w->control_mode == RSB_PD_PLUS_FEEDFORWARD_TORQUE && i >= 1;
+    if (rk4_contact) img[L.t_model + i * L.model_pitch + 28] = 0.f;      // (its generalized force carries inertial terms, the effort clip was applied in the stages)
+    const bool pd = w->control_mode == RSB_PD_PLUS_FEEDFORWARD_TORQUE && !rk4_contact && i >= 1;
     img[L.t_gain + 2 * i] = pd ? w->h_kp[i + 5] : 0.f;
     img[L.t_gain + 2 * i + 1] = pd ? w->h_kd[i + 5] : 0.f;
     put_i(L.t_parlv + i, (b.parent[i] + 1) | (b.level[i] << 8));
@@ -458,11 +459,11 @@ std::vector<float> build_lds_image(const rsb_world* w, const LdsLayout& L) {
 }
 
 // the step kernel's per-block tables (build_lds_image) in layout L and the self-collision pairs' materials, re-uploaded when a setter dirtied them
-// or the image was built for another layout.  Joins (stream_of): callers that must not join later - a closed-loop run with its action stage in
+// or the image was built for another layout or the other kind of launch.  Joins (stream_of): callers that must not join later - a closed-loop run with its action stage in
 // flight - call it up front.
-int upload_image(rsb_world* w, const LdsLayout& L) {
-  if (!w->image_dirty && std::memcmp(&L, &w->image_layout, sizeof L) == 0) return RSB_OK;
-    std::vector<float> img = build_lds_image(w, L);
+int upload_image(rsb_world* w, const LdsLayout& L, bool rk4_contact) {
+  if (!w->image_dirty && rk4_contact == w->image_rk4_contact && std::memcmp(&L, &w->image_layout, sizeof L) == 0) return RSB_OK;
+    std::vector<float> img = build_lds_image(w, L, rk4_contact);
     HIP_TRY(hipMemcpyAsync(w->d_image, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice, stream_of(w)));
     const int np = n_self_pairs(w);
     std::vector<float> mat((size_t)4 * np, 0.f);
@@ -482,42 +483,12 @@ int upload_image(rsb_world* w, const LdsLayout& L) {
     }
     HIP_TRY(hipStreamSynchronize(stream_of(w)));   // img / mat are stack-lifetime buffers
     w->image_dirty = false;
-    w->image_layout = L;
+    w->image_layout = L; w->image_rk4_contact = rk4_contact;
   return RSB_OK;
 }
 
-int do_integrate(rsb_world* w, int nsub) {
-  HIP_TRY(hipSetDevice(w->device));
-  if (w->integ_rk4 && !w->rk4_inner) return rk4_integrate(w, nsub);      // IntegrationScheme::RUNGE_KUTTA_4: host-driven over the query kernels (rsb_rk4.hip)
-  // what this launch fuses and its env mask: taken off the world first, so that a refused launch leaves neither to the next one
-  const rsb_world::Fuse f = w->fuse;
-  w->fuse = rsb_world::Fuse();
-  const uint8_t* const mask = w->launch_mask;
-  w->launch_mask = nullptr;
-  int st = check_lpe(w, effective_lpe(w));
-  if (st != RSB_OK) return st;
-  // the kernel class: a resident launch runs K control steps in this ONE launch; a pipelined one goes to one of the two private streams, behind a
-  // gate that lets it start only when the launch before it (on the other stream) has been dispatched completely - its workgroups wait for their
-  // predecessors' envs (open loop) or for the action stage's rows (closed loop), which therefore must all be running or done (no deadlock: a waiting
-  // workgroup never keeps a predecessor off the chip).  rsb_pipeline.hip holds the bookkeeping.
-  const bool resident = f.res_steps > 0;
-  const bool closed_loop = f.closed_loop;      // a step of rsb_closed_loop_run: waits for the action stage's word instead of its predecessor's
-  LaunchKind kind;
-  kind.peer = f.peer;
-  kind.pipelined = !resident && f.pipeline && (!f.env_task || closed_loop) && pipelining_allowed(w, f.peer, mask);
-  if (resident) {
-    kind.res_stage = f.res_stage;
-    if (f.res_stage == 2) for (int l = 0; l <= f.res_mlp.n_layers; ++l) kind.mlp_width = std::max(kind.mlp_width, (int)f.res_mlp.dims[l]);
-  }
-  StepClass c;
-  st = choose_step_class(w, kind, &c);
-  if (st != RSB_OK) return st;
-  if (resident && mask) { rsb::set_error("no resident launch with an env mask"); return RSB_E_UNSUPPORTED; }
-  const LdsLayout L = world_layout(w);
-  const size_t lds_bytes = lds_bytes_of(L, c.lpe);
-  const int blocks = (w->N + 64 / c.lpe - 1) / (64 / c.lpe);
-  StepArgs a;
-  std::memset(&a, 0, sizeof a);
+// do_integrate, part 2: everything of StepArgs that follows from the world's configuration alone (L, c: the launch's layout and kernel class)
+void fill_world_args(const rsb_world* w, const LdsLayout& L, const StepClass& c, StepArgs& a) {
   a.model = w->d_model;
   a.gc = w->d_gc; a.gv = w->d_gv; a.ptarget = w->d_pt; a.dtarget = w->d_dt; a.tauff = w->d_tff;
 #ifndef RSB_X_READ_ZERO_ROWS      /* (A/B switch: read the rows although they are known to be zero, as rounds 1-4 did) */
@@ -530,48 +501,13 @@ int do_integrate(rsb_world* w, int nsub) {
   a.heights = w->d_heights;
   a.hm_index = w->d_hm_index;
   a.warm = w->warm_start ? w->d_warm : nullptr;
-  st = upload_image(w, L);
-  if (st != RSB_OK) return st;
-  a.lds_image = w->d_image;
-  if (f.ptarget_src) { a.ptarget = f.ptarget_src; a.ptarget_store = w->d_pt; }
-  if (f.act) { a.act = f.act; a.act_mean = w->d_env_mean; a.act_std = w->env_cfg.action_std; a.ptarget_store = w->d_pt; a.tau2_out = w->d_env_tau2; }
-  uint8_t* env_done = nullptr;
-  if (f.env_task) {   // rsb_env_step: reward, termination, reset and the next observation in this launch's epilogue
-    a.env_reward = f.env_reward; a.env_ob = f.env_ob; env_done = f.env_done;
-    a.env_fwd_coeff = w->env_cfg.forward_vel_coeff; a.env_fwd_clip = w->env_cfg.forward_vel_clip;
-    a.env_torque_coeff = w->env_cfg.torque_coeff; a.env_terminal_reward = w->env_cfg.terminal_reward;
-    a.tau2_out = nullptr;
-  }
-  a.obs_out = f.obs_out; a.obs_idx = f.obs_idx; a.obs_slots = f.obs_slots;
-  if (f.peer) {   // rsb_control_step with the peer-mapped obs exchange connected: rows go to every rank's gathered buffer of this step's parity
-    rsb_world::Peer& P = w->peer;
-    const uint32_t step = ++P.step;
-    const int par = (int)(step & 1u);
-    const size_t bufsz = (size_t)P.ranks * w->N * P.od;
-    for (int p = 0; p < P.ranks; ++p) {
-      float* pb = static_cast<float*>(P.peer_base[p]);
-      a.obs_peer[p] = pb + (size_t)par * bufsz;
-      a.obs_flag[p] = reinterpret_cast<uint32_t*>(pb + 2 * bufsz) + (size_t)par * RSB_MAX_RANKS + P.rank;
-    }
-    a.obs_ctr = reinterpret_cast<uint32_t*>(static_cast<float*>(P.base) + 2 * bufsz) + 2 * RSB_MAX_RANKS;
-    a.n_obs_peers = P.ranks; a.obs_row0 = P.rank * w->N; a.obs_step = step;
-    a.obs_slots = P.slots; a.obs_idx = P.idx.empty() ? nullptr : P.d_idx;
-  }
-  a.early_term = (w->early_term && f.have_allowed) ? 1 : 0;
-  a.do_reset = f.do_reset; a.allowed = f.allowed; a.gc0 = f.gc0; a.gv0 = f.gv0; a.reset_rows = f.rows;
-  if (!a.do_reset) { a.gc0 = w->d_gc; a.gv0 = w->d_gv; a.reset_rows = w->N; }   // never dereferenced, but keep the pointers valid
-  if (resident) {
-    a.res_steps = f.res_steps; a.res_full = w->res_full ? 1 : 0;
-    a.res_targets = f.res_targets; a.res_period = f.res_period; a.res_first = f.res_first;
-    a.res_obs_stride = f.res_obs_stride; a.res_done_stride = f.res_done_stride; a.res_pass_global0 = f.res_pass_global0;
-    if (f.res_stage == 1) a.res_pol.lin = f.res_lin;
-    if (f.res_stage == 2) a.res_pol.mlp = f.res_mlp;
-    if (f.res_stage == 0) { a.ptarget = f.res_targets + (size_t)(f.res_first % f.res_period) * ((size_t)w->N * w->blob.nq); a.ptarget_store = w->d_pt; }
-  }
+  a.lds_image = w->d_image; a.L = L; a.lds_floats = (int)(lds_bytes_of(L, c.lpe) / sizeof(float));
+  a.gc0 = w->d_gc; a.gv0 = w->d_gv; a.reset_rows = w->N;      // (no reset: never dereferenced, but keep the pointers valid)
+  a.tau_out = w->want_genf ? w->d_genf : nullptr;
   a.prof = w->d_prof;
   a.dbg = w->dbg_env >= 0 ? w->d_dbg : nullptr;
   a.dbg_env = w->dbg_env;
-  a.N = w->N; a.nsub = nsub; a.kmax = w->kmax; a.control_mode = w->control_mode;
+  a.N = w->N; a.kmax = w->kmax; a.control_mode = w->control_mode;
   a.nb = w->blob.nb; a.nq = w->blob.nq; a.nv = w->blob.nv; a.ncol = w->blob.ncol; a.depth = w->blob.depth;
   a.cw = round4(6 + w->blob.depth - 1); a.max_kid = w->max_kid; a.fixed_base = w->blob.fixed_base; a.chain = (w->chain && c.lpe == 16) ? 1 : 0;
   // (2: the quad form of the up pass - its 48-float hand-over slots need the square Delassus layout's rows to themselves: the packed layout keeps the joint factors there)
@@ -595,51 +531,126 @@ int do_integrate(rsb_world* w, int nsub) {
     a.hm_max = w->hm_max;
   }
   a.n_self = n_self_pairs(w); a.self_mat = w->d_self_mat;
-  a.L = L;
   static const bool poison = std::getenv("RSB_POISON_LDS") != nullptr;  // debug aid, see tests/test_gpu_properties.py
   a.poison_lds = poison ? 1 : 0;
   static const bool prof_fine = std::getenv("RSB_PROF_FINE") != nullptr;  // debug aid: also time searches / Newton steps / epilogues
   a.prof_fine = prof_fine ? 1 : 0;
-  a.lds_floats = (int)(lds_bytes / sizeof(float));
-  a.done_out = env_done ? env_done : f.res_done ? f.res_done : w->d_done_out;
-  a.tau_out = w->want_genf ? w->d_genf : nullptr;
-  a.env_mask = mask;
+}
+
+// do_integrate, part 3: what THIS launch is asked for on top (a successful launch's only side effect on the world here: the peer exchange's step counter)
+void apply_request(rsb_world* w, const StepRequest& f, StepArgs& a) {
+  if (f.rk4_contact) { a.control_mode = RSB_FORCE_AND_TORQUE; a.integ_theta = 1.f; a.tauff = w->d_tff; }      // (tau_eff lives in d_tff for this launch)
+  if (f.ptarget_src) { a.ptarget = f.ptarget_src; a.ptarget_store = w->d_pt; }
+  if (f.act) { a.act = f.act; a.act_mean = w->d_env_mean; a.act_std = w->env_cfg.action_std; a.ptarget_store = w->d_pt; a.tau2_out = w->d_env_tau2; }
+  if (f.env_task) {   // rsb_env_step: reward, termination, reset and the next observation in this launch's epilogue
+    a.env_reward = f.env_reward; a.env_ob = f.env_ob;
+    a.env_fwd_coeff = w->env_cfg.forward_vel_coeff; a.env_fwd_clip = w->env_cfg.forward_vel_clip;
+    a.env_torque_coeff = w->env_cfg.torque_coeff; a.env_terminal_reward = w->env_cfg.terminal_reward;
+    a.tau2_out = nullptr;
+  }
+  a.obs_out = f.obs_out; a.obs_idx = f.obs_idx; a.obs_slots = f.obs_slots;
+  if (f.peer) {   // rsb_control_step with the peer-mapped obs exchange connected: rows go to every rank's gathered buffer of this step's parity
+    rsb_world::Peer& P = w->peer;
+    const uint32_t step = ++P.step;
+    const int par = (int)(step & 1u);
+    const size_t bufsz = (size_t)P.ranks * w->N * P.od;
+    for (int p = 0; p < P.ranks; ++p) {
+      float* pb = static_cast<float*>(P.peer_base[p]);
+      a.obs_peer[p] = pb + (size_t)par * bufsz;
+      a.obs_flag[p] = reinterpret_cast<uint32_t*>(pb + 2 * bufsz) + (size_t)par * RSB_MAX_RANKS + P.rank;
+    }
+    a.obs_ctr = reinterpret_cast<uint32_t*>(static_cast<float*>(P.base) + 2 * bufsz) + 2 * RSB_MAX_RANKS;
+    a.n_obs_peers = P.ranks; a.obs_row0 = P.rank * w->N; a.obs_step = step;
+    a.obs_slots = P.slots; a.obs_idx = P.idx.empty() ? nullptr : P.d_idx;
+  }
+  a.early_term = (w->early_term && f.have_allowed) ? 1 : 0; a.allowed = f.allowed;
+  if (f.do_reset) { a.do_reset = f.do_reset; a.gc0 = f.gc0; a.gv0 = f.gv0; a.reset_rows = f.rows; }
+  if (f.res_steps > 0) {
+    a.res_steps = f.res_steps; a.res_full = w->res_full ? 1 : 0;
+    a.res_targets = f.res_targets; a.res_period = f.res_period; a.res_first = f.res_first;
+    a.res_obs_stride = f.res_obs_stride; a.res_done_stride = f.res_done_stride; a.res_pass_global0 = f.res_pass_global0;
+    if (f.res_stage == 1) a.res_pol.lin = f.res_lin;
+    if (f.res_stage == 2) a.res_pol.mlp = f.res_mlp;
+    if (f.res_stage == 0) { a.ptarget = f.res_targets + (size_t)(f.res_first % f.res_period) * ((size_t)w->N * w->blob.nq); a.ptarget_store = w->d_pt; }
+  }
+  a.done_out = f.redirect_done ? f.done_out : w->d_done_out;
+  a.env_mask = f.mask;
+}
+
+// do_integrate, part 4: the launch goes to its stream - one of the pipeline's private ones behind its gate (rsb_pipeline.hip), else the world's
+int enqueue_step(rsb_world* w, const StepRequest& f, bool pipelined, const StepClass& c, StepArgs& a) {
+  const int blocks = (w->N + 64 / c.lpe - 1) / (64 / c.lpe);
   hipStream_t ls = nullptr;
-  if (kind.pipelined) {
-    st = pipe_begin_launch(w, a, blocks, closed_loop, &ls);
+  if (pipelined) {
+    int st = pipe_begin_launch(w, a, blocks, f.closed_loop, &ls);
     if (st != RSB_OK) return st;
-    if (!w->pipe_log_suppress) {      // what a faulted pipeline replays in lock-step (pipe_recover)
+    if (!f.closed_loop) {      // what a faulted pipeline replays in lock-step (pipe_recover); a closed-loop run has logged itself
       rsb_world::PipeLog e;
-      e.f = f; e.nsub = nsub; e.done_out = w->d_done_out;
+      e.req = f; e.nsub = a.nsub; e.req.pipeline = false;
+      if (!f.redirect_done) { e.req.redirect_done = true; e.req.done_out = w->d_done_out; }      // (rsb_set_done_output does not join: the buffer of NOW)
       w->pipe_log.push_back(e);
     }
-    w->pipe_time_logged += nsub * w->dt;
+    w->pipe_time_logged += a.nsub * w->dt;
   } else {
     ls = stream_of(w);
     if (w->pipe_dep) { HIP_TRY(hipStreamWaitEvent(ls, w->pipe_dep, 0)); w->pipe_dep = nullptr; }
   }
-  w->launch_stream = ls;
   hipEvent_t e0 = w->ev0, e1 = w->ev1;
   const bool rec = w->timing && (w->launch_index++ % w->timing_stride == 0);
   if (rec && !w->ring0.empty()) { e0 = w->ring0[w->ring_next]; e1 = w->ring1[w->ring_next]; }
   if (rec) HIP_TRY(hipEventRecord(e0, ls));
   // a specialised code object of the class (rsb_spec.hip): same kernel, the model's dimensions and the world's switches as constants; else the ahead-of-time instance
+  const size_t lds_bytes = lds_bytes_of(a.L, c.lpe);
   const hipFunction_t spec_fn = spec_find(w, c, a);
-  st = spec_fn ? spec_launch(spec_fn, a, blocks, lds_bytes, ls) : launch_instance(c, a, blocks, lds_bytes, ls);
+  const int st = spec_fn ? spec_launch(spec_fn, a, blocks, lds_bytes, ls) : launch_instance(c, a, blocks, lds_bytes, ls);
   if (st != RSB_OK) return st;
   ++(spec_fn ? w->spec_launches : w->generic_launches);
-  if (resident) ++w->res_launches;
-  if (kind.pipelined) pipe_end_launch(w, a, ls);
+  if (f.res_steps > 0) ++w->res_launches;
+  if (pipelined) pipe_end_launch(w, a, ls);
   if (rec) {
     HIP_TRY(hipEventRecord(e1, ls));
     if (!w->ring0.empty()) { w->ring_next = (w->ring_next + 1) % w->ring0.size(); if (w->ring_count < w->ring0.size()) ++w->ring_count; }
   }
-  w->world_time += (double)std::max(f.res_steps, 1) * nsub * w->dt;
+  w->world_time += (double)std::max(f.res_steps, 1) * a.nsub * w->dt;
   w->integrate1_valid = false;
   // (the fused epilogue left the observation the NEXT step starts from in the world's own buffer - unless the caller holds raw pointers to the state rows
   //  and may write through them behind the library's back: then every closed-loop run recomputes its first observation, as the lock-step path does)
   w->env_ob_valid = a.env_ob != nullptr && a.env_ob == w->d_env_ob && !w->raw_state;
   return RSB_OK;
+}
+
+// EVERY launch of the step kernel.  What it should do beyond the world's configuration arrives in the request and nowhere else: a refused launch
+// has written nothing to the world, and nothing on the world is rewritten for the duration of a launch.
+int do_integrate(rsb_world* w, int nsub, const StepRequest& f) {
+  HIP_TRY(hipSetDevice(w->device));
+  if (w->integ_rk4 && !f.rk4_contact) return rk4_integrate(w, nsub, f);      // IntegrationScheme::RUNGE_KUTTA_4: host-driven over the query kernels (rsb_rk4.hip)
+  int st = check_lpe(w, effective_lpe(w));
+  if (st != RSB_OK) return st;
+  // part 1, the kernel class: a resident launch runs K control steps in this ONE launch; a pipelined one goes to one of the two private streams, behind a
+  // gate that lets it start only when the launch before it (on the other stream) has been dispatched completely - its workgroups wait for their
+  // predecessors' envs (open loop) or for the action stage's rows (closed loop), which therefore must all be running or done (no deadlock: a waiting
+  // workgroup never keeps a predecessor off the chip).  rsb_pipeline.hip holds the bookkeeping.
+  const bool resident = f.res_steps > 0;
+  LaunchKind kind;
+  kind.peer = f.peer; kind.rk4_contact = f.rk4_contact;
+  kind.pipelined = !resident && f.pipeline && (!f.env_task || f.closed_loop) && pipelining_allowed(w, f.peer, f.mask);
+  if (resident) {
+    kind.res_stage = f.res_stage;
+    if (f.res_stage == 2) for (int l = 0; l <= f.res_mlp.n_layers; ++l) kind.mlp_width = std::max(kind.mlp_width, (int)f.res_mlp.dims[l]);
+  }
+  StepClass c;
+  st = choose_step_class(w, kind, &c);
+  if (st != RSB_OK) return st;
+  if (resident && f.mask) { rsb::set_error("no resident launch with an env mask"); return RSB_E_UNSUPPORTED; }
+  const LdsLayout L = world_layout(w);
+  st = upload_image(w, L, f.rk4_contact);      // (joins - before the pipeline's bookkeeping begins)
+  if (st != RSB_OK) return st;
+  StepArgs a;
+  std::memset(&a, 0, sizeof a);
+  fill_world_args(w, L, c, a);
+  apply_request(w, f, a);
+  a.nsub = nsub;
+  return enqueue_step(w, f, kind.pipelined, c, a);
 }
 
 // does a field the caller uploads hold nothing but zeros?  (host data: looked at; device data: unknown -> no)
@@ -662,20 +673,37 @@ int copy_out(rsb_world* w, void* dst, const void* src, size_t bytes, int space) 
   return RSB_OK;
 }
 
-int launch_dynamics_query(rsb_world* w, hipStream_t s) {
+// ONE launch per vectorised step of the env task: action -> PD targets in the prologue, control_dt / simulation_dt sub-steps, then reward,
+// termination (non-foot contact or non-finite state), reset and the next observation in the epilogue
+StepRequest env_task_request(const rsb_world* w, const float* act, float* reward, float* ob, uint8_t* done) {
+  StepRequest f;
+  f.act = act;
+  f.have_allowed = 1; f.allowed = w->env_allowed;
+  f.do_reset = 1; f.gc0 = w->d_env_gc0; f.gv0 = w->d_env_gv0; f.rows = 1;
+  if (w->d_env_gc0_rows) { f.gc0 = w->d_env_gc0_rows; f.gv0 = w->d_env_gv0_rows; f.rows = w->N; }      // rsb_env_set_reset_states
+  f.env_task = true; f.env_reward = reward; f.env_ob = ob; f.redirect_done = done != nullptr; f.done_out = done;
+  return f;
+}
+
+// the (M, h) query kernel on the current state, into d_M / d_h (allocated at the first use)
+int launch_mh_query(rsb_world* w, hipStream_t s) {
   const size_t N = w->N, nv = w->blob.nv;
   if (!w->d_M) {
     HIP_TRY(hipMalloc(&w->d_M, N * nv * nv * sizeof(float)));
     HIP_TRY(hipMalloc(&w->d_h, N * nv * sizeof(float)));
   }
+  rsbq::QueryArgs qa;
+  qa.model = w->d_model; qa.gc = w->d_gc; qa.gv = w->d_gv; qa.M = w->d_M; qa.h = w->d_h; qa.N = w->N;
+  qa.gx = (float)w->gravity[0]; qa.gy = (float)w->gravity[1]; qa.gz = (float)w->gravity[2];
+  return rsbq::launch_query(qa, w->blob.nb, s) == 0 ? RSB_OK : RSB_E_HIP;
+}
+int launch_dynamics_query(rsb_world* w, hipStream_t s) {
+  const size_t N = w->N, nv = w->blob.nv;
   if (!w->d_Minv) {
     HIP_TRY(hipMalloc(&w->d_Minv, N * nv * nv * sizeof(float)));
     HIP_TRY(hipMalloc(&w->d_Mwork, N * nv * nv * sizeof(float)));
   }
-  rsbq::QueryArgs qa;
-  qa.model = w->d_model; qa.gc = w->d_gc; qa.gv = w->d_gv; qa.M = w->d_M; qa.h = w->d_h; qa.N = w->N;
-  qa.gx = (float)w->gravity[0]; qa.gy = (float)w->gravity[1]; qa.gz = (float)w->gravity[2];
-  if (rsbq::launch_query(qa, w->blob.nb, s) != 0) { rsb::set_error("RUNGE_KUTTA_4: query kernel launch failed"); return RSB_E_HIP; }
+  if (launch_mh_query(w, s) != RSB_OK) { rsb::set_error("RUNGE_KUTTA_4: query kernel launch failed"); return RSB_E_HIP; }
   hipLaunchKernelGGL(rsbq::rsb_minv_kernel, dim3((w->N + 63) / 64), dim3(64), 0, s, w->d_M, w->d_Mwork, w->d_Minv, w->N, w->blob.nv);
   HIP_TRY(hipGetLastError());
   return RSB_OK;
@@ -1160,7 +1188,7 @@ int rsb_set_generalized_force(rsb_world* w, const float* tau, int space) {
 
 int rsb_integrate(rsb_world* w, int n_substeps) {
   if (!w || n_substeps < 1) { rsb::set_error("rsb_integrate: n_substeps must be >= 1"); return RSB_E_INVALID; }
-  return do_integrate(w, n_substeps);
+  return do_integrate(w, n_substeps, StepRequest());
 }
 
 int rsb_integrate_masked(rsb_world* w, int n_substeps, const uint8_t* mask, int space) {
@@ -1173,8 +1201,9 @@ int rsb_integrate_masked(rsb_world* w, int n_substeps, const uint8_t* mask, int 
     HIP_TRY(hipStreamSynchronize(stream_of(w)));   // pageable host memory: the caller may reuse its buffer
     dmask = w->d_launch_mask;
   }
-  w->launch_mask = dmask;
-  return do_integrate(w, n_substeps);
+  StepRequest req;
+  req.mask = dmask;
+  return do_integrate(w, n_substeps, req);
 }
 
 int rsb_host_alloc(size_t bytes, void** out) {
@@ -1252,8 +1281,9 @@ int rsb_view_exchange(rsb_world* w, const rsb_view_io* io) {
   w->view_prof[0] += lap_ns(tp);
   for (int i = 0; i < io->n_launches; ++i) {
     if (io->launch_substeps[i] < 1) { rsb::set_error("rsb_view_exchange: launch_substeps must be >= 1"); return RSB_E_INVALID; }
-    if (io->launch_masks) w->launch_mask = w->d_view_masks + (size_t)i * N;
-    const int st = do_integrate(w, io->launch_substeps[i]);
+    StepRequest req;
+    if (io->launch_masks) req.mask = w->d_view_masks + (size_t)i * N;
+    const int st = do_integrate(w, io->launch_substeps[i], req);
     if (st != RSB_OK) return st;
   }
   w->view_prof[1] += lap_ns(tp);
@@ -1290,22 +1320,13 @@ int rsb_set_done_output(rsb_world* w, uint8_t* done_device) {
 int rsb_integrate1(rsb_world* w) {
   if (!w) return RSB_E_INVALID;
   HIP_TRY(hipSetDevice(w->device));
-  const size_t N = w->N, nv = w->blob.nv;
-  if (!w->d_M) {
-    HIP_TRY(hipMalloc(&w->d_M, N * nv * nv * sizeof(float)));
-    HIP_TRY(hipMalloc(&w->d_h, N * nv * sizeof(float)));
-  }
-  rsbq::QueryArgs qa;
-  qa.model = w->d_model; qa.gc = w->d_gc; qa.gv = w->d_gv; qa.M = w->d_M; qa.h = w->d_h; qa.N = w->N;
-  qa.gx = (float)w->gravity[0]; qa.gy = (float)w->gravity[1]; qa.gz = (float)w->gravity[2];
-  int st = rsbq::launch_query(qa, w->blob.nb, stream_of(w));
-  if (st != 0) { rsb::set_error("integrate1: query kernel launch failed"); return RSB_E_HIP; }
+  if (launch_mh_query(w, stream_of(w)) != RSB_OK) { rsb::set_error("integrate1: query kernel launch failed"); return RSB_E_HIP; }
   w->integrate1_valid = true;
   return RSB_OK;
 }
 int rsb_integrate2(rsb_world* w) {
   if (!w) return RSB_E_INVALID;
-  return do_integrate(w, 1);
+  return do_integrate(w, 1, StepRequest());
 }
 
 int rsb_get_contacts(rsb_world* w, int32_t* counts, rsb_contact* contacts, int space) {
@@ -1364,6 +1385,28 @@ int upload_obs_idx(rsb_world* w, const int32_t* idx, int n) {
     HIP_TRY(hipMemcpyAsync(w->d_obs_idx, w->obs_idx_host.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, stream_of(w)));
     HIP_TRY(hipStreamSynchronize(stream_of(w)));
   }
+  return RSB_OK;
+}
+// the parts of a control step's request that rsb_control_step and rsb_control_steps share: the observation block gathered in the epilogue ...
+int request_obs(rsb_world* w, float* obs_out, const int32_t* force_collisions, int n_force_slots, StepRequest* f) {
+  if (!obs_out) return RSB_OK;
+  f->obs_out = obs_out; f->obs_slots = n_force_slots;
+  if (force_collisions && n_force_slots > 0) {
+    int st = upload_obs_idx(w, force_collisions, n_force_slots);
+    if (st != RSB_OK) return st;
+    f->obs_idx = w->d_obs_idx;
+  }
+  return RSB_OK;
+}
+// ... and the reset of the envs that touched the ground with a primitive outside the allowed set (who: the caller's name in the error message)
+int request_reset(const rsb_world* w, const char* who, const int32_t* allowed_collisions, int n_allowed, const float* gc0, const float* gv0, int rows, StepRequest* f) {
+  if (!gc0) return RSB_OK;
+  unsigned long long allowed = 0;
+  for (int i = 0; i < n_allowed; ++i) {
+    if (allowed_collisions[i] < 0 || allowed_collisions[i] >= w->blob.ncol) { rsb::set_error(std::string(who) + ": collision index out of range"); return RSB_E_INVALID; }
+    allowed |= 1ull << allowed_collisions[i];
+  }
+  f->do_reset = 1; f->have_allowed = 1; f->allowed = allowed; f->gc0 = gc0; f->gv0 = gv0; f->rows = rows;
   return RSB_OK;
 }
 }  // namespace
@@ -1442,9 +1485,10 @@ int rsb_reset_terminated(rsb_world* w, const int32_t* allowed_collisions, int n_
 
 // One control step of a vectorised env, enqueued with a single call: PD targets in, n_substeps x integrate(),
 // observation block out, terminated envs reset.  All pointers are device pointers; nothing synchronises.
-int rsb_control_step(rsb_world* w, const float* p_target, const float* d_target, int n_substeps, float* obs_out,
-                     const int32_t* force_collisions, int n_force_slots, const int32_t* allowed_collisions,
-                     int n_allowed, const float* gc0, const float* gv0, int rows) {
+// (done_out: where THIS step's done flags go instead of the world's rsb_set_done_output buffer; NULL: there)
+static int control_step(rsb_world* w, const float* p_target, const float* d_target, int n_substeps, float* obs_out,
+                        const int32_t* force_collisions, int n_force_slots, const int32_t* allowed_collisions,
+                        int n_allowed, const float* gc0, const float* gv0, int rows, uint8_t* done_out) {
   if (!w || n_substeps < 1 || n_force_slots < 0 || n_force_slots > RSB_MAX_COLLISIONS || n_allowed < 0 ||
       (n_allowed > 0 && !allowed_collisions) || ((gc0 != nullptr) != (gv0 != nullptr)) || (gc0 && rows != 1 && rows != w->N)) {
     rsb::set_error("rsb_control_step: bad argument");
@@ -1460,7 +1504,7 @@ int rsb_control_step(rsb_world* w, const float* p_target, const float* d_target,
     if (st != RSB_OK) return st;
   }
   if (d_target) { int st = copy_in(w, w->d_dt, d_target, (size_t)w->N * w->blob.nv, RSB_DEVICE); if (st) return st; w->dt_zero = false; }
-  rsb_world::Fuse f;
+  StepRequest f;
   f.ptarget_src = p_target;   // read in place by the launch, which also refreshes the world's own copy
   f.pipeline = p_target != nullptr && d_target == nullptr;   // (rsb_set_step_pipelining: control steps that upload nothing may overlap)
   if (w->peer.connected) {
@@ -1473,24 +1517,15 @@ int rsb_control_step(rsb_world* w, const float* p_target, const float* d_target,
     }
     f.peer = true;
   }
-  if (obs_out) {
-    f.obs_out = obs_out; f.obs_slots = n_force_slots;
-    if (force_collisions && n_force_slots > 0) {
-      int st = upload_obs_idx(w, force_collisions, n_force_slots);
-      if (st != RSB_OK) return st;
-      f.obs_idx = w->d_obs_idx;
-    }
-  }
-  if (gc0) {
-    unsigned long long allowed = 0;
-    for (int i = 0; i < n_allowed; ++i) {
-      if (allowed_collisions[i] < 0 || allowed_collisions[i] >= w->blob.ncol) { rsb::set_error("rsb_control_step: collision index out of range"); return RSB_E_INVALID; }
-      allowed |= 1ull << allowed_collisions[i];
-    }
-    f.do_reset = 1; f.have_allowed = 1; f.allowed = allowed; f.gc0 = gc0; f.gv0 = gv0; f.rows = rows;
-  }
-  w->fuse = f;
-  return rsb_integrate(w, n_substeps);
+  int st = request_obs(w, obs_out, force_collisions, n_force_slots, &f);
+  if (st == RSB_OK) st = request_reset(w, "rsb_control_step", allowed_collisions, n_allowed, gc0, gv0, rows, &f);
+  if (st != RSB_OK) return st;
+  f.redirect_done = done_out != nullptr; f.done_out = done_out;
+  return do_integrate(w, n_substeps, f);
+}
+int rsb_control_step(rsb_world* w, const float* p_target, const float* d_target, int n_substeps, float* obs_out, const int32_t* force_collisions,
+                     int n_force_slots, const int32_t* allowed_collisions, int n_allowed, const float* gc0, const float* gv0, int rows) {
+  return control_step(w, p_target, d_target, n_substeps, obs_out, force_collisions, n_force_slots, allowed_collisions, n_allowed, gc0, gv0, rows, nullptr);
 }
 
 // K control steps of the open loop (rsb.h): ONE resident launch when residency is on and the world's class has a resident twin, else K control steps
@@ -1509,37 +1544,19 @@ int rsb_control_steps(rsb_world* w, int n_steps, const float* p_targets, int per
   LaunchKind open_loop;
   open_loop.res_stage = 0;
   if (!(w->res_on && choose_step_class(w, open_loop, &c) == RSB_OK)) {
-    uint8_t* const saved = w->d_done_out;
     int st = RSB_OK;
-    for (int j = 0; j < n_steps && st == RSB_OK; ++j) {
-      if (done_out) w->d_done_out = done_out + (size_t)j * (size_t)done_step_stride;
-      st = rsb_control_step(w, p_targets + (size_t)((first + j) % period) * slice, nullptr, n_substeps, obs_out ? obs_out + (size_t)j * (size_t)obs_step_stride : nullptr,
-                            force_collisions, n_force_slots, allowed_collisions, n_allowed, gc0, gv0, rows);
-    }
-    w->d_done_out = saved;
+    for (int j = 0; j < n_steps && st == RSB_OK; ++j)
+      st = control_step(w, p_targets + (size_t)((first + j) % period) * slice, nullptr, n_substeps, obs_out ? obs_out + (size_t)j * (size_t)obs_step_stride : nullptr,
+                        force_collisions, n_force_slots, allowed_collisions, n_allowed, gc0, gv0, rows, done_out ? done_out + (size_t)j * (size_t)done_step_stride : nullptr);
     return st;
   }
-  rsb_world::Fuse f;
-  if (obs_out) {
-    f.obs_out = obs_out; f.obs_slots = n_force_slots;
-    if (force_collisions && n_force_slots > 0) {
-      int st = upload_obs_idx(w, force_collisions, n_force_slots);
-      if (st != RSB_OK) return st;
-      f.obs_idx = w->d_obs_idx;
-    }
-  }
-  if (gc0) {
-    unsigned long long allowed = 0;
-    for (int i = 0; i < n_allowed; ++i) {
-      if (allowed_collisions[i] < 0 || allowed_collisions[i] >= w->blob.ncol) { rsb::set_error("rsb_control_steps: collision index out of range"); return RSB_E_INVALID; }
-      allowed |= 1ull << allowed_collisions[i];
-    }
-    f.do_reset = 1; f.have_allowed = 1; f.allowed = allowed; f.gc0 = gc0; f.gv0 = gv0; f.rows = rows;
-  }
+  StepRequest f;
+  int st = request_obs(w, obs_out, force_collisions, n_force_slots, &f);
+  if (st == RSB_OK) st = request_reset(w, "rsb_control_steps", allowed_collisions, n_allowed, gc0, gv0, rows, &f);
+  if (st != RSB_OK) return st;
   f.res_steps = n_steps; f.res_stage = 0; f.res_targets = p_targets; f.res_period = period; f.res_first = first;
-  f.res_obs_stride = obs_out ? obs_step_stride : 0; f.res_done_stride = done_out ? done_step_stride : 0; f.res_done = done_out;   // (a stride without its buffer must not walk the world's own done flags)
-  w->fuse = f;
-  return do_integrate(w, n_substeps);
+  f.res_obs_stride = obs_out ? obs_step_stride : 0; f.res_done_stride = done_out ? done_step_stride : 0; f.redirect_done = done_out != nullptr; f.done_out = done_out;   // (a stride without its buffer must not walk the world's own done flags)
+  return do_integrate(w, n_substeps, f);
 }
 int rsb_set_step_residency(rsb_world* w, int on) {
   if (!w) { rsb::set_error("rsb_set_step_residency: null world"); return RSB_E_INVALID; }
@@ -1662,18 +1679,7 @@ int rsb_env_step(rsb_world* w, const float* action, float* reward, uint8_t* done
   float* drew = space == RSB_DEVICE ? reward : (reward ? w->d_env_reward : nullptr);
   uint8_t* ddone = space == RSB_DEVICE ? done : (done ? w->d_env_done : nullptr);
   float* dob = ob_next ? (space == RSB_DEVICE ? ob_next : w->d_env_ob) : nullptr;
-  {
-    // ONE launch per vectorised step: action -> PD targets in the prologue, control_dt / simulation_dt sub-steps, then reward,
-    // termination (non-foot contact or non-finite state), reset and the next observation in the epilogue
-    rsb_world::Fuse f;
-    f.act = dact;
-    f.have_allowed = 1; f.allowed = w->env_allowed;
-    f.do_reset = 1; f.gc0 = w->d_env_gc0; f.gv0 = w->d_env_gv0; f.rows = 1;
-    if (w->d_env_gc0_rows) { f.gc0 = w->d_env_gc0_rows; f.gv0 = w->d_env_gv0_rows; f.rows = w->N; }      // rsb_env_set_reset_states
-    f.env_task = true; f.env_reward = drew; f.env_ob = dob; f.env_done = ddone;
-    w->fuse = f;
-  }
-  st = do_integrate(w, w->env_cfg.n_substeps);
+  st = do_integrate(w, w->env_cfg.n_substeps, env_task_request(w, dact, drew, dob, ddone));
   if (st != RSB_OK) return st;
   w->integrate1_valid = false; w->env_ob_valid = false;
   if (space == RSB_HOST) {
