@@ -179,6 +179,10 @@ int rsb_debug_resident_full_writes(rsb_world* w, int on);
  * (4 x 40 048 B for the ANYmal-like model, 3 workgroups for the Atlas-like one), and a table that grows by a few hundred bytes can cost a quarter or a third of the
  * resident waves (tests/test_kernel_budget.py pins the counts). */
 int rsb_model_lds_bytes(const rsb_model* m, int kmax, int self_collision, int lanes_per_env);
+/* host only (no GPU): where the step kernel keeps the Delassus blocks of this model in an env's LDS region.  Returns the contact capacity of the kernel class (8 or
+ * 16) and fills out4 = { floats of the region, floats between the block rows of two contacts (0: the packed-triangular storage of the 16-slot classes), floats per
+ * 3x3 block, floats of a dense row (the region's size is 3 x capacity x this in the 8-slot classes) }: block (i, k) starts at out4[1] * i + out4[2] * k. */
+int rsb_model_delassus_layout(const rsb_model* m, int kmax, int self_collision, int* out4);
 /* host only (no GPU): does the step kernel run the up pass of this model on four lanes per body (specialised code objects, 16 lanes per env, <= 8 contact
  * slots)?  It does for a base with four consecutively numbered serial chains of equal length, <= 16 bodies - every tree level below the base then holds four bodies.
  * Returns the number of levels below the base and fills table[(level - 1) * 4 + quad] with the body that quad works on (table may be NULL; capacity in ints), 0 for

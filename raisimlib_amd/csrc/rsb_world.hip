@@ -159,6 +159,8 @@ static LdsLayout make_layout_pitch(const rsb_model_blob& b, int kcap, int n_self
   // the up pass's [nb][28] hand-over slots and the height-map narrow phase's scratch alias the Delassus rows
   // (packed layout: [hand-over slots | joint factors] of the up pass - the factors are last read by the contact columns, before the
   // Delassus phase writes its blocks over both)
+  // (square classes: the kernel stores one row of kcap 12-float blocks per contact, step_types.h: g_row_pitch - inside the dense rows' 3 kcap x gstride floats, which stay the region's size)
+  static_assert(rsbk::g_row_pitch(8) <= 3 * (4 * 8 + 4), "the block rows of the Delassus phase must fit the region of the dense rows");
   const int gsize = tri ? (kcap * (kcap + 1) / 2) * 12 : 3 * kcap * L.gstride;
   const int upsize = b.nb * rsbk::kUpSlot + (tri ? b.nb * rsbk::kFactSlot : 0);
   L.g = take(std::max({gsize, upsize, (rsbk::kHmRec + 8) * hm_slots_for(b) + RSB_MAX_COLLISIONS + 16}));   // (+ 16: the capsule search's four sample results)
@@ -338,6 +340,15 @@ extern "C" int rsb_model_lds_bytes(const rsb_model* m, int kmax, int self_collis
   const int n_self = self_collision ? (int)rsbw::enumerate_self_pairs(b, std::vector<uint8_t>()).size() / 2 : 0;
   const int lpe = lanes_per_env ? lanes_per_env : rsbw::default_lpe(b, kmax, n_self);
   return (int)rsbw::lds_bytes_for(b, rsbw::kcap_of(b, kmax), lpe, n_self);
+}
+extern "C" int rsb_model_delassus_layout(const rsb_model* m, int kmax, int self_collision, int* out4) {
+  if (!m || !out4 || kmax < 1 || kmax > RSB_MAX_CONTACTS) { rsb::set_error("rsb_model_delassus_layout: bad argument"); return RSB_E_INVALID; }
+  const rsb_model_blob& b = m->blob;
+  const int n_self = self_collision ? (int)rsbw::enumerate_self_pairs(b, std::vector<uint8_t>()).size() / 2 : 0;
+  const int kcap = rsbw::kcap_of(b, kmax);
+  const rsbk::LdsLayout L = rsbw::make_layout(b, kcap, n_self);
+  out4[0] = L.ginv - L.g; out4[1] = kcap > 8 ? 0 : rsbk::g_row_pitch(kcap); out4[2] = rsbk::kGBlock; out4[3] = L.gstride;
+  return kcap;
 }
 extern "C" int rsb_model_up_quads(const rsb_model* m, int* table, int capacity) {
   if (!m) { rsb::set_error("rsb_model_up_quads: null model"); return RSB_E_INVALID; }

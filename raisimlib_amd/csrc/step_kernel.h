@@ -148,6 +148,33 @@ __device__ __forceinline__ void tri_store(float* G, int a, int b, const float (&
   }
 }
 
+// ---- Delassus storage of the quadruped classes (KMAX <= 8), row-block form (step_types.h: g_row_pitch): a block is 12 floats {g00 g10 g01 g11 | g02 g12 g20 g21 | g22 -}.
+// gblk_load / gblk_store move M[r][c] = G[3 i + r][3 k + c] between registers and the block at p; gblk_add is the self-collision fold's pass over one pair of blocks
+// (every entry one addition, pads included - the Delassus phase wrote zeros there).  RSB_G_ROWS 0 (-DRSB_X_G_SQUARE): the dense rows of round 1, for an A/B and a bit-for-bit comparison.
+#ifdef RSB_X_G_SQUARE
+#define RSB_G_ROWS 0
+#else
+#define RSB_G_ROWS 1
+#endif
+__device__ __forceinline__ void gblk_load(const float* p, float (&M)[3][3]) {
+  float a[4], b[4];
+  ld4(p, a); ld4(p + 4, b);
+  M[0][0] = a[0]; M[1][0] = a[1]; M[0][1] = a[2]; M[1][1] = a[3];
+  M[0][2] = b[0]; M[1][2] = b[1]; M[2][0] = b[2]; M[2][1] = b[3];
+  M[2][2] = p[8];
+}
+__device__ __forceinline__ void gblk_store(float* p, const float (&M)[3][3]) {
+  const float a[4] = {M[0][0], M[1][0], M[0][1], M[1][1]}, b[4] = {M[0][2], M[1][2], M[2][0], M[2][1]}, c[4] = {M[2][2], 0.f, 0.f, 0.f};
+  st4(p, a); st4(p + 4, b); st4(p + 8, c);
+}
+__device__ __forceinline__ void gblk_add(float* dst, float* src) {   // dst += src, src = 0
+  float a[12], b[12];
+  const float z[12] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  ldv<3>(dst, a); ldv<3>(src, b);
+  RSB_UNROLL for (int e = 0; e < 12; ++e) a[e] += b[e];
+  stv<3>(dst, a); stv<3>(src, z);
+}
+
 // ---- resident closed loop: pass `pass` of the action stage for env block `blk`, evaluated by the block's own wave (stage_bodies.h).  The rows the
 // body reads (observation, reward, done) were written by this wave's epilogue: the stores have to have arrived (vmcnt) and the wave's L1 must not
 // serve an older copy of the lines (buffer_inv); likewise behind it for the action rows the next control step reads.
@@ -201,6 +228,8 @@ __global__ void __launch_bounds__(64) RSB_X_WPE_ATTR rsb_step_kernel(const StepA
   static_assert(!RES || (CL & ~(64 | 128 | 256)) == 0, "resident launches exist for the plain floating-base class");
   static_assert(RES == (RSB_RESIDENT != 0), "the control-step loop of the resident classes is selected by the preprocessor (RSB_I_CL)");
   constexpr bool TRI = KMAX > 8;    // packed lower-triangular Delassus blocks (see tri_off); the quadruped classes keep the square layout
+  [[maybe_unused]] constexpr bool GROWS = !TRI && RSB_G_ROWS != 0;   // ... in the row-block form (gblk_load)
+  [[maybe_unused]] constexpr int GRP = g_row_pitch(KMAX);           // floats between the block rows of two contacts
   const int lane = threadIdx.x;
   const int el = lane / LPE;
   const int s = lane - el * LPE;

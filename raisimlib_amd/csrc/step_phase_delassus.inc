@@ -58,6 +58,11 @@
               const float row[4] = {acc[cc], acc[3 + cc], acc[6 + cc], 0.f};
               st4(bp + 4 * cc, row);
             }
+          } else if constexpr (GROWS) {   // block (i, j) into contact i's row and its transpose into contact j's: 3 + 3 16-byte stores (the diagonal pair writes once)
+            const float B[3][3] = {{acc[0], acc[1], acc[2]}, {acc[3], acc[4], acc[5]}, {acc[6], acc[7], acc[8]}};
+            const float Bt[3][3] = {{acc[0], acc[3], acc[6]}, {acc[1], acc[4], acc[7]}, {acc[2], acc[5], acc[8]}};
+            gblk_store(G + i * GRP + kGBlock * j, B);
+            if (i != j) gblk_store(G + j * GRP + kGBlock * i, Bt);
           } else {
             RSB_UNROLL for (int rr = 0; rr < 3; ++rr)
               RSB_UNROLL for (int cc = 0; cc < 3; ++cc) {
@@ -79,15 +84,21 @@
         // is rank deficient; the same small compliance as for a self-collision (whose fold below adds it for those)
         if (s < nc && __float_as_int(CON[s * kConSlot + 11]) < kSelfA) {
           float acc[9], gi[12];
-          float* dg = TRI ? G + tri_off(s, s) : G + 3 * s * GS + 4 * s;     // the diagonal block's rows, dgs floats apart
+          float* dg = TRI ? G + tri_off(s, s) : (GROWS ? G + s * GRP + kGBlock * s : G + 3 * s * GS + 4 * s);     // the diagonal block (TRI, dense rows: its rows, dgs floats apart)
           const int dgs = TRI ? 4 : GS;
-          RSB_UNROLL for (int rr = 0; rr < 3; ++rr) {
-            float g4[4];
-            ld4(dg + rr * dgs, g4);
-            acc[3 * rr] = g4[0]; acc[3 * rr + 1] = g4[1]; acc[3 * rr + 2] = g4[2];
+          if constexpr (GROWS) {
+            float D[3][3];
+            gblk_load(dg, D);
+            RSB_UNROLL for (int rr = 0; rr < 3; ++rr) RSB_UNROLL for (int cc = 0; cc < 3; ++cc) acc[3 * rr + cc] = D[rr][cc];
+          } else {
+            RSB_UNROLL for (int rr = 0; rr < 3; ++rr) {
+              float g4[4];
+              ld4(dg + rr * dgs, g4);
+              acc[3 * rr] = g4[0]; acc[3 * rr + 1] = g4[1]; acc[3 * rr + 2] = g4[2];
+            }
           }
           const float reg = kSelfReg * (acc[0] + acc[4] + acc[8]) * (1.0f / 3.0f);
-          RSB_UNROLL for (int rr = 0; rr < 3; ++rr) { acc[4 * rr] += reg; dg[rr * dgs + rr] = acc[4 * rr]; }
+          RSB_UNROLL for (int rr = 0; rr < 3; ++rr) { acc[4 * rr] += reg; dg[GROWS ? g_block_off(rr, rr) : rr * dgs + rr] = acc[4 * rr]; }
           inv3(acc, gi);
           gi[9] = gi[10] = gi[11] = 0.f;
           stv<3>(GINV + 12 * s, gi);
@@ -139,15 +150,21 @@
             continue;
           }
           if (prim && s < nc) {       // rows: lane = column block
-            RSB_UNROLL for (int rr = 0; rr < 3; ++rr) {
-              float ga[4], gb[4];
-              ld4(G + (3 * sa + rr) * GS + 4 * s, ga); ld4(G + (3 * sb + rr) * GS + 4 * s, gb);
-              RSB_UNROLL for (int e = 0; e < 4; ++e) ga[e] += gb[e];
-              st4(G + (3 * sa + rr) * GS + 4 * s, ga); st4(G + (3 * sb + rr) * GS + 4 * s, z4);
+            if constexpr (GROWS) {
+              gblk_add(G + sa * GRP + kGBlock * s, G + sb * GRP + kGBlock * s);
+            } else {
+              RSB_UNROLL for (int rr = 0; rr < 3; ++rr) {
+                float ga[4], gb[4];
+                ld4(G + (3 * sa + rr) * GS + 4 * s, ga); ld4(G + (3 * sb + rr) * GS + 4 * s, gb);
+                RSB_UNROLL for (int e = 0; e < 4; ++e) ga[e] += gb[e];
+                st4(G + (3 * sa + rr) * GS + 4 * s, ga); st4(G + (3 * sb + rr) * GS + 4 * s, z4);
+              }
             }
           }
           __syncthreads();
-          if (prim) {                 // columns: lane = row
+          if constexpr (GROWS) {      // columns: lane = row block (the three rows of contact s in one pass)
+            if (prim && s < nc) gblk_add(G + s * GRP + kGBlock * sa, G + s * GRP + kGBlock * sb);
+          } else if (prim) {          // columns: lane = row
             for (int r = s; r < 3 * nc; r += LPE) {
               float ga[4], gb[4];
               ld4(G + r * GS + 4 * sa, ga); ld4(G + r * GS + 4 * sb, gb);
@@ -162,23 +179,29 @@
             const float ju = m4[3] + SELFT[4 * sb + 3];   // approach speed of the two bodies' points
             RSB_UNROLL for (int rr = 0; rr < 3; ++rr) { CV[3 * sa + rr] += CV[3 * sb + rr]; CV[3 * sb + rr] = 0.f; }
             if (m4[1] > 0.f && ju < -m4[2]) CV[3 * sa + 2] += m4[1] * ju;
-            RSB_UNROLL for (int rr = 0; rr < 3; ++rr) {
-              float g4[4];
-              ld4(G + (3 * sa + rr) * GS + 4 * sa, g4);
-              acc[3 * rr] = g4[0]; acc[3 * rr + 1] = g4[1]; acc[3 * rr + 2] = g4[2];
+            if constexpr (GROWS) {
+              float D[3][3];
+              gblk_load(G + sa * GRP + kGBlock * sa, D);
+              RSB_UNROLL for (int rr = 0; rr < 3; ++rr) RSB_UNROLL for (int cc = 0; cc < 3; ++cc) acc[3 * rr + cc] = D[rr][cc];
+            } else {
+              RSB_UNROLL for (int rr = 0; rr < 3; ++rr) {
+                float g4[4];
+                ld4(G + (3 * sa + rr) * GS + 4 * sa, g4);
+                acc[3 * rr] = g4[0]; acc[3 * rr + 1] = g4[1]; acc[3 * rr + 2] = g4[2];
+              }
             }
             // two bodies joined by fewer than three joints cannot move relative to each other in every direction: the block is
             // rank deficient (thigh against trunk: two joints).  A small compliance keeps the per-contact rule well posed
             // (oracle: ORC_SELF_REG)
             const float reg = (FIXED ? 2.f : 1.f) * kSelfReg * (acc[0] + acc[4] + acc[8]) * (1.0f / 3.0f);
-            RSB_UNROLL for (int rr = 0; rr < 3; ++rr) { acc[4 * rr] += reg; G[(3 * sa + rr) * GS + 4 * sa + rr] = acc[4 * rr]; }
+            RSB_UNROLL for (int rr = 0; rr < 3; ++rr) { acc[4 * rr] += reg; G[GROWS ? sa * GRP + kGBlock * sa + g_block_off(rr, rr) : (3 * sa + rr) * GS + 4 * sa + rr] = acc[4 * rr]; }
             inv3(acc, gi);
             gi[9] = gi[10] = gi[11] = 0.f;
             stv<3>(GINV + 12 * sa, gi);
             RSB_UNROLL for (int q2 = 0; q2 < 12; ++q2) gi[q2] = 0.f;
             gi[0] = gi[4] = gi[8] = 1.f;
             stv<3>(GINV + 12 * sb, gi);
-            RSB_UNROLL for (int rr = 0; rr < 3; ++rr) G[(3 * sb + rr) * GS + 4 * sb + rr] = 1.f;
+            RSB_UNROLL for (int rr = 0; rr < 3; ++rr) G[GROWS ? sb * GRP + kGBlock * sb + g_block_off(rr, rr) : (3 * sb + rr) * GS + 4 * sb + rr] = 1.f;
           }
           __syncthreads();
         }

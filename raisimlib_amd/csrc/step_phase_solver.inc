@@ -4,7 +4,7 @@
         a.dbg[0] = (float)nc_real;
         for (int i = 0; i < n3; ++i)
           for (int j = 0; j < n3; ++j)
-            a.dbg[1 + i * n3 + j] = !TRI ? G[i * GS + 4 * (j / 3) + (j % 3)]
+            a.dbg[1 + i * n3 + j] = GROWS ? G[(i / 3) * GRP + kGBlock * (j / 3) + g_block_off(i % 3, j % 3)] : !TRI ? G[i * GS + 4 * (j / 3) + (j % 3)]
                                           : (i / 3 >= j / 3 ? G[tri_off(i / 3, j / 3) + 4 * (i % 3) + (j % 3)] : G[tri_off(j / 3, i / 3) + 4 * (j % 3) + (i % 3)]);
         for (int i = 0; i < n3; ++i) a.dbg[1 + n3 * n3 + i] = CV[i];
       }
@@ -27,16 +27,22 @@
       {
         const bool isc = s < nc;
         float Gii[9], Ginv[12], v[3], lam[3] = {0.f, 0.f, 0.f};
-        const float* Gmine = G + 3 * min(s, KMAX - 1) * GS;     // non-contact lanes read (and ignore) the last contact's rows
+        const float* Gmine = GROWS ? G + GRP * min(s, KMAX - 1) : G + 3 * min(s, KMAX - 1) * GS;     // non-contact lanes read (and ignore) the last contact's rows
         RSB_UNROLL for (int q2 = 0; q2 < 9; ++q2) Gii[q2] = 0.f;
         RSB_UNROLL for (int q2 = 0; q2 < 12; ++q2) Ginv[q2] = 0.f;
         v[0] = v[1] = v[2] = 0.f;
         int gidc = -1 - s;            // limb of the own contact (non-contact lanes: an id nobody shares)
         if (isc) {
-          RSB_UNROLL for (int rr = 0; rr < 3; ++rr) {
-            float g4[4];
-            ld4(TRI ? G + tri_off(s, s) + 4 * rr : G + (3 * s + rr) * GS + 4 * s, g4);      // blocks sit on a 4-float pitch: one 16-byte read per row
-            Gii[3 * rr] = g4[0]; Gii[3 * rr + 1] = g4[1]; Gii[3 * rr + 2] = g4[2];
+          if constexpr (GROWS) {   // the own block of the own row
+            float D[3][3];
+            gblk_load(Gmine + kGBlock * s, D);
+            RSB_UNROLL for (int rr = 0; rr < 3; ++rr) RSB_UNROLL for (int cc = 0; cc < 3; ++cc) Gii[3 * rr + cc] = D[rr][cc];
+          } else {
+            RSB_UNROLL for (int rr = 0; rr < 3; ++rr) {
+              float g4[4];
+              ld4(TRI ? G + tri_off(s, s) + 4 * rr : G + (3 * s + rr) * GS + 4 * s, g4);      // blocks sit on a 4-float pitch: one 16-byte read per row
+              Gii[3 * rr] = g4[0]; Gii[3 * rr + 1] = g4[1]; Gii[3 * rr + 2] = g4[2];
+            }
           }
           ldv<3>(GINV + 12 * s, Ginv);
           v[0] = CV[3 * s]; v[1] = CV[3 * s + 1]; v[2] = CV[3 * s + 2];
@@ -134,6 +140,13 @@
               RSB_UNROLL for (int cc = 0; cc < 3; ++cc) g[rr][cc] = tr ? t[cc][rr] : t[rr][cc];
               g[rr][3] = 0.f;
             }
+          } else if constexpr (GROWS) {
+            float t[3][3];
+            gblk_load(Gmine + kGBlock * k, t);
+            RSB_UNROLL for (int rr = 0; rr < 3; ++rr) {
+              RSB_UNROLL for (int cc = 0; cc < 3; ++cc) g[rr][cc] = t[rr][cc];
+              g[rr][3] = 0.f;
+            }
           } else {
             RSB_UNROLL for (int rr = 0; rr < 3; ++rr) ld4(Gmine + rr * GS + 4 * k, g[rr]);
           }
@@ -165,9 +178,16 @@
           // (the exchange reads blocks 0-4 whatever the count; 5-7 only behind its `ncw > 5` tests: the usual wave - four or five contacts per env - does not load them)
           RSB_UNROLL for (int k = 0; k < NPK; ++k) {
             if (k < 5 || ncw > 5) {
-              RSB_UNROLL for (int cc = 0; cc < 3; ++cc) {
-                gp[k][cc] = float2v{Gmine[4 * k + cc], Gmine[GS + 4 * k + cc]};
-                gr[k][cc] = Gmine[2 * GS + 4 * k + cc];
+              if constexpr (GROWS) {   // the block is stored as the pairs and the third row: two 16-byte reads and one scalar
+                float q0[4], q1[4];
+                ld4(Gmine + kGBlock * k, q0); ld4(Gmine + kGBlock * k + 4, q1);
+                gp[k][0] = float2v{q0[0], q0[1]}; gp[k][1] = float2v{q0[2], q0[3]}; gp[k][2] = float2v{q1[0], q1[1]};
+                gr[k][0] = q1[2]; gr[k][1] = q1[3]; gr[k][2] = Gmine[kGBlock * k + 8];
+              } else {
+                RSB_UNROLL for (int cc = 0; cc < 3; ++cc) {
+                  gp[k][cc] = float2v{Gmine[4 * k + cc], Gmine[GS + 4 * k + cc]};
+                  gr[k][cc] = Gmine[2 * GS + 4 * k + cc];
+                }
               }
             }
           }

@@ -33,6 +33,15 @@ constexpr int kUpQuadSlot = RSB_X_UPQSLOT;   // quad form of the up pass (step_s
 constexpr int kDownQuadSlot = 12;            // quad form of the down pass (step_spec.h: RSB_DOWN_QUADS): what a body lane parks for the quad that walks its chain: E9 q qd pad (all finite; aliases
                                   // the front of the up pass's slots in the Delassus rows - consumed before those are written)
 static_assert(kDownQuadSlot <= kUpQuadSlot, "the down pass's staging slots lie inside the region the host checks for the up pass's (rsb_world.hip: nb * kUpQuadSlot <= L.ginv - L.g)");
+// Delassus blocks of the square-layout classes (KMAX <= 8), row-block form: contact i owns ONE contiguous row of KMAX blocks, block (i, k) = G[3 i .. 3 i + 2][3 k .. 3 k + 2]
+// sits at g_row_pitch(KMAX) * i + kGBlock * k in the order the solver's registers take it - {g00 g10} {g01 g11} | {g02 g12} g20 g21 | g22 pad3 (rows 0 and 1 of a column
+// are one register pair of the packed exchange) - so that the pair lane of the Delassus phase writes a block with three 16-byte stores and the contact lane of the solver
+// reads it with two 16-byte reads and one scalar.  + 4 floats per row: the eight contact lanes of an env start their 16-byte reads on eight different four-bank groups
+// (100 i mod 64 = 0, 36, 8, 44, 16, 52, 24, 60).  KMAX rows fit inside the 3 KMAX rows of LdsLayout::gstride floats the layout reserves (rsb_world.hip: make_layout_pitch).
+// -DRSB_X_G_SQUARE (RSB_SPEC_EXTRA_DEFS) compiles the dense rows it replaces: [3 KMAX][gstride], a block's rows gstride floats apart - same results bit for bit.
+constexpr int kGBlock = 12;
+__host__ __device__ constexpr int g_row_pitch(int kcap) { return kGBlock * kcap + 4; }
+__host__ __device__ constexpr int g_block_off(int rr, int cc) { return rr < 2 ? 2 * cc + rr : 6 + cc; }   // entry (rr, cc) within its block
 constexpr int kEnvPad = RSB_X_ENVPAD;       // floats added to an env's LDS region (shifts the banks the wave's envs start on)
 constexpr int kFactSlot = 16;    // S6 UD6 rsD invD pad2
 constexpr int kConSlot = 16;     // x3 depth | t1 body | t2 col | n pad

@@ -88,6 +88,15 @@ class Model:
         check(min(n, 0), "rsb_model_up_quads")
         return [[int(t[4 * lv + g]) for g in range(4)] for lv in range(n)]
 
+    def delassus_layout(self, kmax=8, self_collision=True):
+        """Where the step kernel keeps this model's Delassus blocks in an env's LDS region: dict(kcap, floats, row_pitch, block, dense_row) - block (i, k) starts
+        row_pitch * i + block * k floats into the region; row_pitch 0 = the packed-triangular storage of the 16-slot classes (host only; rsb_model_delassus_layout)"""
+        import ctypes
+        t = (ctypes.c_int * 4)()
+        kcap = lib().rsb_model_delassus_layout(self.handle, int(kmax), int(bool(self_collision)), t)
+        check(min(kcap, 0), "rsb_model_delassus_layout")
+        return dict(kcap=kcap, floats=int(t[0]), row_pitch=int(t[1]), block=int(t[2]), dense_row=int(t[3]))
+
     def collision_indices(self, suffix):
         return [i for i, n in enumerate(self.collision_names()) if n.endswith(suffix)]
 
