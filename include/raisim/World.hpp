@@ -259,6 +259,19 @@ class BatchedWorld {
     dropStage(RSB_F_TAU_FF);      // the host mirror of the feed-forward rows is refetched on its next use
   }
 
+  /// ArticulatedSystem::getCOM / getLinearMomentum / getAngularMomentum / getKineticEnergy / getPotentialEnergy for ALL envs in one call, computed on
+  /// the device from the resident state; rows staged through the per-env views are uploaded first.  Host buffers, any may be null (not all):
+  /// com, comVel, linMom [N,3], angMom [N,3] about the centre of mass, kinetic [N], potential [N] = -M g . com with the world's gravity.
+  void getCentroidal(float* com, float* comVel, float* linMom, float* angMom, float* kinetic, float* potential) {
+    std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
+    RSB_CHECK(rsb_get_centroidal(world_, com, comVel, linMom, angMom, kinetic, potential, RSB_HOST));
+  }
+  /// the centroidal momentum matrices A [N,6,dof()]: (linMom, angMom about the centre of mass) = A gv; a fixed-base system keeps its six (zero) base columns
+  void getCentroidalMomentumMatrices(float* A) {
+    std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
+    RSB_CHECK(rsb_get_centroidal_momentum_matrix(world_, A, RSB_HOST));
+  }
+
   /// HeightMap::getHeight / getNormal for ALL envs in one call, on the device, each env on its own terrain: xy [N,P,2] world coordinates ->
   /// height [N,P], normal [N,P,3] (unit normal of the triangle under the point; either may be null).  Coordinates outside the map are clamped to it;
   /// a ground plane gives its height and (0, 0, 1).  Host buffers.
@@ -757,6 +770,38 @@ class ArticulatedSystem {
   }
   void clearExternalForces() { VecDyn tau(getDOF()); putRow(RSB_F_TAU_FF, tau); }
 
+  // ---- whole-body quantities (slow path, correctness only: this env's row on the host, in double; BatchedWorld::getCentroidal is the fast path).
+  // Every body contributes its mass; a fixed base does not move.  Angular momentum about `referencePoint` (world frame): L_c + (c - p) x P.
+  const Vec<3>& getCOM() { wholeBody(); return com_; }
+  void getLinearMomentum(Vec<3>& linearMomentum) { wholeBody(); linearMomentum = linMom_; }
+  void getAngularMomentum(const Vec<3>& referencePoint, Vec<3>& angularMomentum) {
+    wholeBody();
+    const double d[3] = {com_[0] - referencePoint[0], com_[1] - referencePoint[1], com_[2] - referencePoint[2]};
+    angularMomentum[0] = angMomC_[0] + d[1] * linMom_[2] - d[2] * linMom_[1];
+    angularMomentum[1] = angMomC_[1] + d[2] * linMom_[0] - d[0] * linMom_[2];
+    angularMomentum[2] = angMomC_[2] + d[0] * linMom_[1] - d[1] * linMom_[0];
+  }
+  double getKineticEnergy() { wholeBody(); return kinetic_; }
+  double getPotentialEnergy(const Vec<3>& gravity) {
+    wholeBody();
+    return -totalMass_ * (gravity[0] * com_[0] + gravity[1] * com_[1] + gravity[2] * com_[2]);
+  }
+  double getEnergy(const Vec<3>& gravity) { const double U = getPotentialEnergy(gravity); return U + kinetic_; }
+#ifdef RAISIM_HAS_EIGEN
+  template <class D> void getLinearMomentum(Eigen::MatrixBase<D>& linearMomentum) { Vec<3> v; getLinearMomentum(v); linearMomentum.derived() = v.e(); }
+  template <class A, class D> void getAngularMomentum(const Eigen::MatrixBase<A>& referencePoint, Eigen::MatrixBase<D>& angularMomentum) {
+    Vec<3> p, v;
+    for (int k = 0; k < 3; ++k) p[k] = referencePoint.derived().coeff(k, 0);
+    getAngularMomentum(p, v); angularMomentum.derived() = v.e();
+  }
+  template <class A> double getPotentialEnergy(const Eigen::MatrixBase<A>& gravity) {
+    Vec<3> g;
+    for (int k = 0; k < 3; ++k) g[k] = gravity.derived().coeff(k, 0);
+    return getPotentialEnergy(g);
+  }
+  template <class A> double getEnergy(const Eigen::MatrixBase<A>& gravity) { const double U = getPotentialEnergy(gravity); return U + kinetic_; }
+#endif
+
   void getBaseOrientation(Mat<3, 3>& rot) {
     const VecDyn& q = fullGc();
     const double w = q[3], x = q[4], y = q[5], z = q[6];
@@ -857,6 +902,49 @@ class ArticulatedSystem {
       J = Jj;
     }
   }
+  // centre of mass, momentum and kinetic energy of this env from its row: body velocities down the tree, then the sums over the bodies
+  //   w_i = w_p (+ a_i qd_i, revolute)      v_i = v_p + w_p x (p_i - p_p) (+ a_i qd_i, prismatic)      v_ci = v_i + w_i x R_i com_i
+  void wholeBody() {
+    fk();
+    const rsb_model_blob& b = w_->blob();
+    if ((int)fullu_.size() != w_->dof()) fullu_.resize(w_->dof());
+    w_->readRow(RSB_F_GV, env_, fullu_.data(), w_->dof());
+    const bool moves = !isFixedBase();
+    std::vector<double> v(3 * b.nb, 0.0), w(3 * b.nb, 0.0);
+    for (int c = 0; c < 3; ++c) { v[c] = moves ? fullu_[c] : 0.0; w[c] = moves ? fullu_[3 + c] : 0.0; }
+    double M = 0, mc[3] = {0, 0, 0}, P[3] = {0, 0, 0}, L0[3] = {0, 0, 0}, T = 0;
+    for (int i = 0; i < b.nb; ++i) {
+      double* vi = &v[3 * i]; double* wi = &w[3 * i];
+      double qd = 0;
+      if (i >= 1) {
+        const int p = b.parent[i];
+        const double* vp = &v[3 * p]; const double* wp = &w[3 * p]; const double* a = &fkA_[3 * i];
+        const double d[3] = {fkP_[3 * i] - fkP_[3 * p], fkP_[3 * i + 1] - fkP_[3 * p + 1], fkP_[3 * i + 2] - fkP_[3 * p + 2]};
+        qd = fullu_[5 + i];
+        const bool rev = b.jtype[i] == RSB_JOINT_REVOLUTE;
+        vi[0] = vp[0] + wp[1] * d[2] - wp[2] * d[1]; vi[1] = vp[1] + wp[2] * d[0] - wp[0] * d[2]; vi[2] = vp[2] + wp[0] * d[1] - wp[1] * d[0];
+        for (int c = 0; c < 3; ++c) { wi[c] = wp[c] + (rev ? a[c] * qd : 0.0); vi[c] += rev ? 0.0 : a[c] * qd; }
+      }
+      const double* R = &fkR_[9 * i];
+      const double* I = b.inertia[i];
+      double rc[3], wb[3], Iwb[3], Iw[3];
+      for (int r = 0; r < 3; ++r) rc[r] = R[3 * r] * b.com[i][0] + R[3 * r + 1] * b.com[i][1] + R[3 * r + 2] * b.com[i][2];
+      const double ci[3] = {fkP_[3 * i] + rc[0], fkP_[3 * i + 1] + rc[1], fkP_[3 * i + 2] + rc[2]};
+      const double vc[3] = {vi[0] + wi[1] * rc[2] - wi[2] * rc[1], vi[1] + wi[2] * rc[0] - wi[0] * rc[2], vi[2] + wi[0] * rc[1] - wi[1] * rc[0]};
+      for (int c = 0; c < 3; ++c) wb[c] = R[c] * wi[0] + R[3 + c] * wi[1] + R[6 + c] * wi[2];      // R^T w
+      Iwb[0] = I[0] * wb[0] + I[1] * wb[1] + I[2] * wb[2]; Iwb[1] = I[1] * wb[0] + I[3] * wb[1] + I[4] * wb[2]; Iwb[2] = I[2] * wb[0] + I[4] * wb[1] + I[5] * wb[2];
+      for (int r = 0; r < 3; ++r) Iw[r] = R[3 * r] * Iwb[0] + R[3 * r + 1] * Iwb[1] + R[3 * r + 2] * Iwb[2];
+      const double m = b.mass[i];
+      M += m;
+      for (int c = 0; c < 3; ++c) { mc[c] += m * ci[c]; P[c] += m * vc[c]; }
+      L0[0] += Iw[0] + m * (ci[1] * vc[2] - ci[2] * vc[1]); L0[1] += Iw[1] + m * (ci[2] * vc[0] - ci[0] * vc[2]); L0[2] += Iw[2] + m * (ci[0] * vc[1] - ci[1] * vc[0]);
+      T += 0.5 * m * (vc[0] * vc[0] + vc[1] * vc[1] + vc[2] * vc[2]) + 0.5 * (wb[0] * Iwb[0] + wb[1] * Iwb[1] + wb[2] * Iwb[2]) + 0.5 * b.armature[i] * qd * qd;
+    }
+    RSFATAL_IF(!(M > 0), "ArticulatedSystem: the total mass is not positive");
+    totalMass_ = M; kinetic_ = T;
+    for (int c = 0; c < 3; ++c) { com_[c] = mc[c] / M; linMom_[c] = P[c]; }
+    angMomC_[0] = L0[0] - (com_[1] * P[2] - com_[2] * P[1]); angMomC_[1] = L0[1] - (com_[2] * P[0] - com_[0] * P[2]); angMomC_[2] = L0[2] - (com_[0] * P[1] - com_[1] * P[0]);
+  }
   void mulJ(const MatDyn& J, Vec<3>& out) {
     const VecDyn& u = getGeneralizedVelocity();
     for (int c = 0; c < 3; ++c) { double sacc = 0; for (size_t d = 0; d < J.cols(); ++d) sacc += J(c, d) * u[d]; out[c] = sacc; }
@@ -864,7 +952,9 @@ class ArticulatedSystem {
   BatchedWorld* w_;
   int env_;
   std::string name_;
-  VecDyn gc_, gv_, h_, fullq_, gf_;
+  VecDyn gc_, gv_, h_, fullq_, fullu_, gf_;
+  Vec<3> com_, linMom_, angMomC_;
+  double totalMass_ = 0, kinetic_ = 0;
   std::vector<double> fkR_, fkP_, fkA_;
   MatDyn M_, Minv_;
   std::vector<Contact> contacts_;

@@ -285,6 +285,25 @@ int rsb_get_frame_jacobians(rsb_world* w, const rsb_frame* frames, int n_frames,
 int rsb_add_external_wrench(rsb_world* w, const rsb_frame* frame, const float* force, const float* torque,
                             const uint8_t* mask, int space);
 
+/* Whole-body quantities of ALL envs in one call, from the resident state [RECALL upstream's per-object ArticulatedSystem::getCOM / getLinearMomentum /
+ * getAngularMomentum / getKineticEnergy / getPotentialEnergy / getEnergy]: HIP kernels on the world's stream, like the frame queries above (ordered with
+ * lock-step, pipelined and resident steps; a pipelined world is joined first); the RSB_DEVICE form does not synchronise, the RSB_HOST form stages through
+ * the same device buffer.  Outputs in `space`, any may be NULL (not all), float32.  The base quaternion is normalised first.  Every body of the blob
+ * contributes its mass.  Fixed-base model: the base does not move, whatever the base entries of gv hold.  A model whose total mass is not positive:
+ * RSB_E_UNSUPPORTED.  An error touches no output. */
+int rsb_get_centroidal(rsb_world* w,
+                       float* com,        /* [N,3] world position of the centre of mass                         */
+                       float* com_vel,    /* [N,3] = lin_mom / total mass                                       */
+                       float* lin_mom,    /* [N,3] sum m_i v_ci                                                 */
+                       float* ang_mom,    /* [N,3] about the CENTRE OF MASS (L_p = L_c + (c - p) x P elsewhere) */
+                       float* kinetic,    /* [N] incl. 0.5 * armature_i * qd_i^2                                */
+                       float* potential,  /* [N] = - total mass * g . com, g = rsb_set_gravity's vector          */
+                       int space);
+/* centroidal momentum matrix A [N,6,nv]: (lin_mom, ang_mom about the COM) = A gv, gv in this ABI's order (base linear, base angular, joints); rows 0-2
+ * linear, rows 3-5 angular.  A[:,3:6,3:6] is the composite inertia about the COM in the world frame, A[:,0:3,:] / total mass the COM Jacobian.
+ * Fixed-base model: the six base columns are zero. */
+int rsb_get_centroidal_momentum_matrix(rsb_world* w, float* A, int space);
+
 /* Terrain queries of ALL envs in one call [RECALL upstream's per-object HeightMap::getHeight / getNormal and World::rayTest, called per env on the
  * host]: HIP kernels on the world's stream, like the frame queries above; the RSB_DEVICE forms do not synchronise, the RSB_HOST forms stage through
  * the same device buffer.  They work on a ground plane and on a height map; with per-env maps (rsb_set_heightmaps) every env reads its own map.  The

@@ -201,6 +201,8 @@ PROTOTYPES = {
     "rsb_get_frame_kinematics": (_I, [_VP, C.POINTER(Frame), _I, _FP, _FP, _FP, _FP, _I]),
     "rsb_get_frame_jacobians": (_I, [_VP, C.POINTER(Frame), _I, _FP, _FP, _I]),
     "rsb_add_external_wrench": (_I, [_VP, C.POINTER(Frame), _FP, _FP, _FP, _I]),
+    "rsb_get_centroidal": (_I, [_VP, _FP, _FP, _FP, _FP, _FP, _FP, _I]),
+    "rsb_get_centroidal_momentum_matrix": (_I, [_VP, _FP, _I]),
     "rsb_get_terrain_height": (_I, [_VP, _FP, _I, _FP, _FP, _I]),
     "rsb_height_scan": (_I, [_VP, C.POINTER(Frame), _I, _FP, _I, _I, _FP, C.c_longlong, _I]),
     "rsb_ray_test": (_I, [_VP, _FP, _FP, _I, C.c_float, _FP, _I]),

@@ -551,6 +551,27 @@ class BatchedWorld:
             space = RSB_HOST
         check(self.L.rsb_add_external_wrench(self.handle, arr, *ptrs, space), "rsb_add_external_wrench")
 
+    # -- whole-body quantities of every env in one call (rsb_centroidal.hip) ------------------------------------------------
+    def centroidal(self, com=True, com_vel=False, lin_mom=False, ang_mom=False, kinetic=False, potential=False, out=None):
+        """ArticulatedSystem::getCOM / getLinearMomentum / getAngularMomentum / getKineticEnergy / getPotentialEnergy of every env at once ->
+        {"com": [N, 3], "com_vel": [N, 3], "lin_mom": [N, 3], "ang_mom": [N, 3] (about the centre of mass), "kinetic": [N], "potential": [N]
+        (= -M g . com with set_gravity's vector)}, world frame, the outputs asked for only.  out: see _frame_outputs."""
+        names = ("com", "com_vel", "lin_mom", "ang_mom", "kinetic", "potential")
+        shapes = {n: (self.N, 3) for n in names[:4]}
+        shapes.update(kinetic=(self.N,), potential=(self.N,))
+        want = dict(com=com, com_vel=com_vel, lin_mom=lin_mom, ang_mom=ang_mom, kinetic=kinetic, potential=potential)
+        space, ptrs, out = self._frame_outputs(names, want, shapes, out, "centroidal")
+        check(self.L.rsb_get_centroidal(self.handle, *ptrs, space), "rsb_get_centroidal")
+        return out
+
+    def centroidal_momentum_matrix(self, out=None):
+        """The centroidal momentum matrix of every env: A [N, 6, nv] with (lin_mom, ang_mom about the centre of mass) = A @ gv; A[:, 3:, 3:6] is the
+        composite inertia about the centre of mass, A[:, :3] / total mass the Jacobian of the centre of mass (a fixed-base model keeps its six,
+        zero, base columns).  out: a float32 array or a torch CUDA tensor of N * 6 * nv elements (RSB_DEVICE, no synchronisation)."""
+        space, ptrs, res = self._frame_outputs(("A",), dict(A=True), {"A": (self.N, 6, self.nv)}, None if out is None else {"A": out}, "centroidal_momentum_matrix")
+        check(self.L.rsb_get_centroidal_momentum_matrix(self.handle, ptrs[0], space), "rsb_get_centroidal_momentum_matrix")
+        return res["A"]
+
     # -- terrain: heights, height scans and ray tests of every env in one call (rsb_terrain_query.hip) -------------------
     def _terrain_io(self, what, inputs, out_shapes, out):
         """inputs {name: (value, shape)}, out_shapes {name: shape}, out {name: array / tensor or None} -> (space, input pointers, output pointers,
