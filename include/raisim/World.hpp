@@ -697,13 +697,13 @@ class ArticulatedSystem {
     for (int i = o; i < nv; ++i) for (int j = o; j < nv; ++j) M_(i - o, j - o) = M[((size_t)env_ * nv + i) * nv + j];
     return M_;
   }
+  /// fixed-base systems: the inverse of the joint block (the base rows and columns of the batch's matrix are zero), as getMassMatrix() returns that block
   const MatDyn& getInverseMassMatrix() {
     const int nv = w_->dof(), o = gvOff();
-    RSFATAL_IF(o != 0, "getInverseMassMatrix: not available for fixed-base systems (the batch inverts the floating-base matrix)");
     std::vector<float> Mi((size_t)w_->numEnvs() * nv * nv);
     w_->getInverseMassMatrices(Mi.data());
-    Minv_.resize(nv, nv);
-    for (int i = 0; i < nv; ++i) for (int j = 0; j < nv; ++j) Minv_(i, j) = Mi[((size_t)env_ * nv + i) * nv + j];
+    Minv_.resize(nv - o, nv - o);
+    for (int i = o; i < nv; ++i) for (int j = o; j < nv; ++j) Minv_(i - o, j - o) = Mi[((size_t)env_ * nv + i) * nv + j];
     return Minv_;
   }
   const VecDyn& getNonlinearities(const Vec<3>& /*gravity*/ = Vec<3>()) {

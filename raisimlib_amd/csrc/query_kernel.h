@@ -47,7 +47,9 @@ __global__ void __launch_bounds__(64) rsb_query_kernel(const QueryArgs a) {
     R0[0] = 1 - 2 * (y * y + z * z); R0[1] = 2 * (x * y - w * z);     R0[2] = 2 * (x * z + w * y);
     R0[3] = 2 * (x * y + w * z);     R0[4] = 1 - 2 * (x * x + z * z); R0[5] = 2 * (y * z - w * x);
     R0[6] = 2 * (x * z - w * y);     R0[7] = 2 * (y * z + w * x);     R0[8] = 1 - 2 * (x * x + y * y);
-    for (int c = 0; c < 3; ++c) { r[0][c] = 0.f; V[0][c] = u[3 + c]; V[0][3 + c] = u[c]; S[0][c] = 0.f; S[0][3 + c] = 0.f; }
+    // a fixed base has no velocity, whatever the caller's rows say (as the step kernel, the oracle and the frame kernels take it)
+    const bool fixed = m.fixed_base != 0;
+    for (int c = 0; c < 3; ++c) { r[0][c] = 0.f; V[0][c] = fixed ? 0.f : u[3 + c]; V[0][3 + c] = fixed ? 0.f : u[c]; S[0][c] = 0.f; S[0][3 + c] = 0.f; }
     float wxv[3];
     cross3(V[0], V[0] + 3, wxv);
     A[0][0] = A[0][1] = A[0][2] = 0.f;
@@ -155,29 +157,31 @@ __global__ void __launch_bounds__(64) rsb_query_kernel(const QueryArgs a) {
 }
 
 // M^-1 per env (slow path): Cholesky M = L L^T, L^-1 by forward substitution, M^-1 = L^-T L^-1, all in global memory.
-// work and out are [N, nv, nv]; M is left untouched.
-__global__ void __launch_bounds__(64) rsb_minv_kernel(const float* M, float* work, float* out, int N, int nv) {
+// work and out are [N, nv, nv]; M is left untouched.  first = 0 inverts the whole matrix (floating base); first = 6 (fixed base) inverts the joint
+// block M[6:, 6:] alone and writes zeros into the base rows and columns: the limit of an infinitely heavy base, which is what the step kernel and
+// the oracle's step integrate (the joint block of the whole matrix's inverse is the response on a base that floats freely).
+__global__ void __launch_bounds__(64) rsb_minv_kernel(const float* M, float* work, float* out, int N, int nv, int first) {
   const int env = blockIdx.x * blockDim.x + threadIdx.x;
   if (env >= N) return;
   const float* Ms = M + (size_t)env * nv * nv;
   float* A = work + (size_t)env * nv * nv;
   float* O = out + (size_t)env * nv * nv;
   for (int i = 0; i < nv * nv; ++i) A[i] = Ms[i];
-  for (int j = 0; j < nv; ++j) {
+  for (int j = first; j < nv; ++j) {
     float d = A[j * nv + j];
-    for (int k = 0; k < j; ++k) d -= A[j * nv + k] * A[j * nv + k];
+    for (int k = first; k < j; ++k) d -= A[j * nv + k] * A[j * nv + k];
     d = sqrtf(d);
     A[j * nv + j] = d;
     const float id = 1.0f / d;
     for (int i = j + 1; i < nv; ++i) {
       float sacc = A[i * nv + j];
-      for (int k = 0; k < j; ++k) sacc -= A[i * nv + k] * A[j * nv + k];
+      for (int k = first; k < j; ++k) sacc -= A[i * nv + k] * A[j * nv + k];
       A[i * nv + j] = sacc * id;
     }
   }
-  for (int i = 0; i < nv; ++i) {           // L -> L^-1 in the lower triangle, row by row
+  for (int i = first; i < nv; ++i) {       // L -> L^-1 in the lower triangle, row by row
     const float ii = 1.0f / A[i * nv + i];
-    for (int j = 0; j < i; ++j) {
+    for (int j = first; j < i; ++j) {
       float sacc = 0.f;
       for (int k = j; k < i; ++k) sacc += A[i * nv + k] * (k == j ? A[j * nv + j] : A[k * nv + j]);
       A[i * nv + j] = -sacc * ii;
@@ -187,7 +191,7 @@ __global__ void __launch_bounds__(64) rsb_minv_kernel(const float* M, float* wor
   for (int a = 0; a < nv; ++a)
     for (int b = 0; b <= a; ++b) {
       float sacc = 0.f;
-      for (int k = a; k < nv; ++k) sacc += A[k * nv + a] * A[k * nv + b];
+      if (b >= first) for (int k = a; k < nv; ++k) sacc += A[k * nv + a] * A[k * nv + b];
       O[a * nv + b] = sacc; O[b * nv + a] = sacc;
     }
 }

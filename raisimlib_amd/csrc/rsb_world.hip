@@ -715,7 +715,7 @@ int launch_dynamics_query(rsb_world* w, hipStream_t s) {
     HIP_TRY(hipMalloc(&w->d_Mwork, N * nv * nv * sizeof(float)));
   }
   if (launch_mh_query(w, s) != RSB_OK) { rsb::set_error("RUNGE_KUTTA_4: query kernel launch failed"); return RSB_E_HIP; }
-  hipLaunchKernelGGL(rsbq::rsb_minv_kernel, dim3((w->N + 63) / 64), dim3(64), 0, s, w->d_M, w->d_Mwork, w->d_Minv, w->N, w->blob.nv);
+  hipLaunchKernelGGL(rsbq::rsb_minv_kernel, dim3((w->N + 63) / 64), dim3(64), 0, s, w->d_M, w->d_Mwork, w->d_Minv, w->N, w->blob.nv, w->blob.fixed_base ? 6 : 0);
   HIP_TRY(hipGetLastError());
   return RSB_OK;
 }
@@ -1363,7 +1363,7 @@ int rsb_get_inverse_mass_matrix(rsb_world* w, float* Minv, int space) {
     HIP_TRY(hipMalloc(&w->d_Minv, n * sizeof(float)));
     HIP_TRY(hipMalloc(&w->d_Mwork, n * sizeof(float)));
   }
-  hipLaunchKernelGGL(rsbq::rsb_minv_kernel, dim3((w->N + 63) / 64), dim3(64), 0, stream_of(w), w->d_M, w->d_Mwork, w->d_Minv, w->N, w->blob.nv);
+  hipLaunchKernelGGL(rsbq::rsb_minv_kernel, dim3((w->N + 63) / 64), dim3(64), 0, stream_of(w), w->d_M, w->d_Mwork, w->d_Minv, w->N, w->blob.nv, w->blob.fixed_base ? 6 : 0);
   HIP_TRY(hipGetLastError());
   return copy_out(w, Minv, w->d_Minv, n * sizeof(float), space);
 }

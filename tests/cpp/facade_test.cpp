@@ -516,6 +516,8 @@ int main(int argc, char** argv) {
       w.integrate1();
       const auto& M = a->getMassMatrix();
       CHECK(M.rows() == 1 && std::fabs(M(0, 0) - 0.25) < 1e-4);                    // m l^2
+      const auto& Mi = a->getInverseMassMatrix();
+      CHECK(Mi.rows() == 1 && Mi.cols() == 1 && std::fabs(Mi(0, 0) - 4.0) < 1e-3);   // 1 / (m l^2): the joint block's inverse, the base held
       raisim::Vec<3> p; a->getFramePosition(1, p);
       CHECK(std::fabs(p[2] - 2.0) < 1e-9);                                          // the hinge sits where the fixed base put it
       double prev = 0.05, t = 0, t0 = -1, t1 = -1;

@@ -11,7 +11,7 @@ arbitrary point of a non-converging iteration, so only boundedness is required t
 import numpy as np
 import pytest
 
-from common import Oracle, f32, standing_states
+from common import Oracle, config_add, f32, rk4_reference, standing_states
 from raisimlib_amd import BatchedWorld, workload
 
 pytestmark = pytest.mark.gpu
@@ -915,37 +915,11 @@ def test_runge_kutta_4_step_against_an_fp64_restatement_over_the_oracles_queries
     kp64, kd64 = kp.astype(np.float64), kd.astype(np.float64)
     dt = workload.DT
 
-    def quat_mul(a, b):
-        return np.array([a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3], a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2],
-                         a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1], a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0]])
-
     def add(q0, th):
-        q = q0.copy()
-        q[:3] += th[:3]
-        ang = np.linalg.norm(th[3:6])
-        d = np.r_[np.cos(ang / 2), (np.sin(ang / 2) / ang if ang > 1e-12 else 0.5) * th[3:6]]
-        q[3:7] = quat_mul(d, q0[3:7]); q[3:7] /= np.linalg.norm(q[3:7])
-        q[7:] += th[6:]
-        return q
+        return config_add(q0, th)
 
-    def accel(q, u, pt):
-        tau = np.zeros(18)
-        tau[6:] = kp64[6:] * (pt[7:] - q[7:]) + kd64[6:] * (0.0 - u[6:])
-        return np.linalg.solve(o.mass_matrix(q), tau - o.nonlinearities(q, u))
-
-    def rk4(q0, u0, pt):
-        ks, kv, th = [], [], np.zeros(18)
-        for i, c in enumerate((0.0, 0.5, 0.5, 1.0)):
-            th = c * dt * kv[-1] if i else np.zeros(18)
-            q = add(q0, th); u = u0 + (c * dt * ks[-1] if i else 0.0)
-            a = accel(q, u, pt)
-            v = u.copy()
-            t3 = th[3:6]
-            v[3:6] = u[3:6] - 0.5 * np.cross(t3, u[3:6]) + np.cross(t3, np.cross(t3, u[3:6])) / 12.0
-            ks.append(a); kv.append(v)
-        du = dt / 6 * (ks[0] + 2 * ks[1] + 2 * ks[2] + ks[3])
-        theta = dt / 6 * (kv[0] + 2 * kv[1] + 2 * kv[2] + kv[3])
-        return theta, du
+    def rk4(q0, u0, pt):                         # (the restatement itself: common.rk4_reference, shared with tests/test_gpu_slow_path.py)
+        return rk4_reference(o, dt, kp64, kd64, q0, u0, pt)
 
     gc, gv = standing_states(N, seed=77, z=(0.45, 0.62), vel=1.0)
     for lift in (1.0, 0.0):                      # in the air / on the ground
