@@ -272,6 +272,26 @@ class BatchedWorld {
     RSB_CHECK(rsb_get_centroidal_momentum_matrix(world_, A, RSB_HOST));
   }
 
+  /// Inverse dynamics for ALL envs in one call, on the device, at the resident state (rows staged through the per-env views are uploaded first):
+  /// tau = M udot + h - J^T loads in the convention of getMassMatrix / getNonlinearities, and the joint reaction wrenches - jointForce / jointTorque
+  /// [N,nb,3]: what body i's parent exerts on body i through joint i, world frame, the torque about the joint's origin.  Host buffers.  udot [N,dof()]
+  /// (null: zeros - gravity compensation at rest); frames with force / torque [N,F,3] (world frame; either may be null; frames may be empty);
+  /// contacts: the contact list of the last sub-step acts too, each record as impulse / dt at its position on its body.  Outputs: any may be null,
+  /// not all.  No PD, damping, effort clip or joint limits enter; the world is left as it was.
+  void inverseDynamics(const float* udot, const std::vector<rsb_frame>& frames, const float* force, const float* torque, bool contacts, float* tau,
+                       float* jointForce, float* jointTorque) {
+    std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
+    RSB_CHECK(rsb_inverse_dynamics(world_, udot, frames.empty() ? nullptr : frames.data(), (int)frames.size(), force, torque, contacts ? RSB_DYN_CONTACTS : 0, tau,
+                                   jointForce, jointTorque, RSB_HOST));
+  }
+  /// Contact-free forward dynamics for ALL envs in one call: udot [N,dof()] = M^-1 (tau - h + J^T loads) by the articulated-body algorithm, the exact
+  /// inverse of inverseDynamics with the same loads.  tau [N,dof()] (null: the feed-forward rows of the world); a fixed base: udot[:, 0:6] = 0.
+  void forwardDynamics(const float* tau, const std::vector<rsb_frame>& frames, const float* force, const float* torque, bool contacts, float* udot) {
+    std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
+    RSB_CHECK(rsb_forward_dynamics(world_, tau, frames.empty() ? nullptr : frames.data(), (int)frames.size(), force, torque, contacts ? RSB_DYN_CONTACTS : 0, udot,
+                                   RSB_HOST));
+  }
+
   /// HeightMap::getHeight / getNormal for ALL envs in one call, on the device, each env on its own terrain: xy [N,P,2] world coordinates ->
   /// height [N,P], normal [N,P,3] (unit normal of the triangle under the point; either may be null).  Coordinates outside the map are clamped to it;
   /// a ground plane gives its height and (0, 0, 1).  Host buffers.

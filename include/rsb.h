@@ -31,6 +31,9 @@
  *                                       <- ArticulatedSystem::getFramePosition/getFrameOrientation/getFrameVelocity/
  *                                          getFrameAngularVelocity/getDenseFrameJacobian/getDenseFrameRotationalJacobian/
  *                                          setExternalForce/setExternalTorque, for all envs in one call
+ *   rsb_inverse_dynamics / rsb_forward_dynamics
+ *                                       <- ArticulatedSystem::setComputeInverseDynamics / getForceAtJointInWorldFrame /
+ *                                          getTorqueAtJointInWorldFrame, and the plain equations of motion, for all envs in one call
  *   rsb_get_terrain_height / rsb_height_scan / rsb_ray_test
  *                                       <- HeightMap::getHeight / getNormal, World::rayTest (against the terrain), for all envs
  *                                          in one call                                (HeightMap.hpp, World.hpp, absent)
@@ -305,6 +308,53 @@ int rsb_get_centroidal(rsb_world* w,
  * linear, rows 3-5 angular.  A[:,3:6,3:6] is the composite inertia about the COM in the world frame, A[:,0:3,:] / total mass the COM Jacobian.
  * Fixed-base model: the six base columns are zero. */
 int rsb_get_centroidal_momentum_matrix(rsb_world* w, float* A, int space);
+
+/* Inverse and contact-free forward dynamics of ALL envs in one call, from the resident state [RECALL upstream's per-object
+ * ArticulatedSystem::setComputeInverseDynamics / getForceAtJointInWorldFrame / getTorqueAtJointInWorldFrame]: HIP kernels on the world's stream, like
+ * the queries above (a pipelined world is joined first); the RSB_DEVICE forms do not synchronise, the RSB_HOST forms stage through the same device
+ * buffer.  Both read the resident gc / gv (the base quaternion normalised first) and the world's gravity (rsb_set_gravity).  Neither changes a bit of
+ * the world: state, warm state, contact records, what rsb_integrate1 left and the feed-forward rows stay as they are.  An error touches no output.
+ *
+ * Convention: that of rsb_get_mass_matrix / rsb_get_nonlinearities,  M udot + h = tau + sum J^T w.  gv / udot: base linear (world velocity of the base
+ * origin), base angular (world), joints; udot is the component-wise time derivative of gv.  tau[0:3] is a world force at the base origin, tau[3:6] a
+ * world torque about it.  M carries the armature on its diagonal, h is Coriolis / centrifugal + gravity.  No PD, no joint damping, no effort clip, no
+ * joint limits: the plain equations of motion.
+ *
+ * External loads: frames is a HOST array of n_frames (0..RSB_MAX_FRAMES; NULL allowed when 0) rsb_frame; force [N,F,3] is a world force applied at the
+ * frame's point, torque [N,F,3] a world torque applied to the frame's body; either may be NULL, not both when n_frames > 0.
+ * flags: RSB_DYN_CONTACTS - every record c < count[e] of env e's resident contact list (RSB_F_CONTACTS, RSB_F_CONTACT_COUNT: the last sub-step's) acts
+ * as the world force impulse / rsb_get_timestep() at `position` on body `body`; both entries of a self-collision act, each on its own body; second-flank
+ * and capsule entries act like any other.  The state is the resident one, after that sub-step.
+ *
+ * rsb_inverse_dynamics:  tau = M(q) udot + h(q,u) - sum_f (J_lin,f^T force_f + J_rot,f^T torque_f) - [RSB_DYN_CONTACTS] sum_c J_c^T (impulse_c / dt),
+ * the total generalized force that must act besides the listed loads for the system to accelerate with udot (NULL: zeros, tau = h - loads).
+ * joint_force[e,i], joint_torque[e,i]: the force and torque body i's PARENT (the world for i = 0) exerts ON body i through joint i, world frame, the
+ * torque about joint i's origin (= body i's frame origin).  This sign convention is ours; upstream's cannot be read from the stub.  The armature is a
+ * rotor: armature_i udot_i is part of tau_i, not of the structural wrench:
+ *     revolute   a_i . joint_torque_i + armature_i udot_i = tau_i        prismatic   a_i . joint_force_i + armature_i udot_i = tau_i
+ *     floating base   (joint_force_0, joint_torque_0) = (tau[0:3], tau[3:6])
+ * rsb_forward_dynamics:  the exact inverse, udot = M^-1 (tau - h + sum J^T w), by the articulated-body algorithm (O(nb) per env, no dense M).
+ * tau NULL: the resident feed-forward rows (RSB_F_TAU_FF).
+ * Fixed-base models: the base neither moves nor accelerates, whatever the base entries of gv, udot and tau hold - no bit of them matters.  Inverse
+ * dynamics: tau[0:6] = (joint_force_0, joint_torque_0) is the wrench the world applies at the base origin to hold the base.  Forward dynamics:
+ * udot[0:6] = 0 and the joint rows solve the joint block (the convention of rsb_get_inverse_mass_matrix).
+ * RSB_E_INVALID, with a message: every output NULL; n_frames < 0 or > RSB_MAX_FRAMES; n_frames > 0 with frames NULL, or with force and torque both
+ * NULL; a frame whose body is out of range or whose offset is not finite; unknown flag bits; a bad `space`. */
+int rsb_inverse_dynamics(rsb_world* w,
+                         const float* udot,            /* [N,nv] in `space`; NULL = zeros                                */
+                         const rsb_frame* frames, int n_frames,
+                         const float* force,           /* [N,F,3] in `space`; may be NULL                                */
+                         const float* torque,          /* [N,F,3] in `space`; may be NULL                                */
+                         int flags,
+                         float* tau,                   /* [N,nv]                                                         */
+                         float* joint_force,           /* [N,nb,3]                                                       */
+                         float* joint_torque,          /* [N,nb,3]   any output may be NULL, not all                     */
+                         int space);
+int rsb_forward_dynamics(rsb_world* w,
+                         const float* tau,             /* [N,nv] in `space`; NULL = the resident feed-forward rows       */
+                         const rsb_frame* frames, int n_frames, const float* force, const float* torque, int flags,
+                         float* udot,                  /* [N,nv]                                                         */
+                         int space);
 
 /* Terrain queries of ALL envs in one call [RECALL upstream's per-object HeightMap::getHeight / getNormal and World::rayTest, called per env on the
  * host]: HIP kernels on the world's stream, like the frame queries above; the RSB_DEVICE forms do not synchronise, the RSB_HOST forms stage through

@@ -123,6 +123,9 @@ typedef enum rsb_scan_mode {
   RSB_SCAN_YAW = 1                /* pattern rotated about z by the frame's heading */
 } rsb_scan_mode;
 
+/* Dynamics queries (rsb_inverse_dynamics, rsb_forward_dynamics; rsb.h): bits of their `flags` argument */
+#define RSB_DYN_CONTACTS 1        /* bit 0: the resident contact list acts, each record as the world force impulse / dt at its position on its body */
+
 #define RSB_MAX_RANKS 8           /* ranks of one node (peer-mapped obs exchange, rsb.h) */
 
 #ifdef __cplusplus

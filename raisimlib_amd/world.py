@@ -572,6 +572,55 @@ class BatchedWorld:
         check(self.L.rsb_get_centroidal_momentum_matrix(self.handle, ptrs[0], space), "rsb_get_centroidal_momentum_matrix")
         return res["A"]
 
+    # -- dynamics: inverse dynamics with joint reaction wrenches, contact-free forward dynamics of every env in one call (rsb_dynamics.hip) ---
+    def _dynamics_inputs(self, what, first, loads, device):
+        """first: udot / tau [N, nv] or None; loads: None or (frames, force, torque) with force / torque [N, F, 3] (either may be None).  Inputs
+        follow the outputs: torch CUDA tensors with torch outputs (RSB_DEVICE), anything else is taken as a float32 host array (RSB_HOST).
+        -> ([first, frames, n, force, torque] as C arguments, what must stay alive until the call returns)"""
+        frames, force, torque = loads if loads is not None else ([], None, None)
+        arr, n = self._frames(frames) if loads is not None else (None, 0)
+        keep, ptrs = [], []
+        for name, v, cnt in ((what[0], first, self.N * self.nv), ("force", force, self.N * n * 3), ("torque", torque, self.N * n * 3)):
+            if v is None:
+                ptrs.append(None)
+            elif device:
+                if not (self._is_torch(v) and v.is_cuda and v.is_contiguous() and str(v.dtype) == "torch.float32" and v.numel() == cnt and v.device.index == self.device):
+                    raise ValueError(f"{what[1]}: {name} must be a contiguous float32 CUDA tensor of {cnt} elements on cuda:{self.device}")
+                ptrs.append(C.c_void_p(v.data_ptr()))
+            else:
+                if self._is_torch(v):
+                    raise ValueError(f"{what[1]}: inputs and outputs must be all torch tensors or all numpy arrays")
+                a = _host(v, np.float32)
+                if a.size != cnt:
+                    raise ValueError(f"{what[1]}: {name} must hold {cnt} elements")
+                keep.append(a)
+                ptrs.append(_hp(a))
+        return [ptrs[0], arr, n, ptrs[1], ptrs[2]], keep
+
+    def inverse_dynamics(self, udot=None, loads=None, contacts=False, tau=True, joint_force=False, joint_torque=False, out=None):
+        """The generalized force that accelerates every env with udot [N, nv] (None: zeros - gravity compensation at rest, h in general) at the
+        resident state, in the convention of get_mass_matrix / get_nonlinearities: tau = M udot + h - J^T loads -> {"tau": [N, nv], "joint_force":
+        [N, nb, 3], "joint_torque": [N, nb, 3]}, the outputs asked for only.  joint_force / joint_torque[e, i]: what body i's parent (the world for
+        i = 0) exerts on body i through joint i, world frame, the torque about joint i's origin.  loads = (frames, force, torque): frames as in
+        frame_kinematics, force [N, F, 3] applied at the frame's point, torque [N, F, 3] applied to its body, world frame, either may be None.
+        contacts=True: the resident contact list acts too, every record as impulse / dt at its position on its body.  No PD, damping, effort clip
+        or joint limits enter.  The world is left as it was.  out: see _frame_outputs; torch outputs take torch inputs (no synchronisation)."""
+        names = ("tau", "joint_force", "joint_torque")
+        shapes = {"tau": (self.N, self.nv), "joint_force": (self.N, self.model.nb, 3), "joint_torque": (self.N, self.model.nb, 3)}
+        space, ptrs, out = self._frame_outputs(names, dict(tau=tau, joint_force=joint_force, joint_torque=joint_torque), shapes, out, "inverse_dynamics")
+        args, keep = self._dynamics_inputs(("udot", "inverse_dynamics"), udot, loads, space == RSB_DEVICE)
+        check(self.L.rsb_inverse_dynamics(self.handle, *args, _capi.RSB_DYN_CONTACTS if contacts else 0, *ptrs, space), "rsb_inverse_dynamics")
+        return out
+
+    def forward_dynamics(self, tau=None, loads=None, contacts=False, out=None):
+        """The acceleration udot [N, nv] the generalized force tau [N, nv] (None: the resident feed-forward rows) produces at the resident state
+        without contact resolution: udot = M^-1 (tau - h + J^T loads), by the articulated-body algorithm; the exact inverse of inverse_dynamics,
+        with its loads and contacts arguments.  A fixed base: udot[:, :6] = 0.  out: a float32 array or a torch CUDA tensor of N * nv elements."""
+        space, ptrs, res = self._frame_outputs(("udot",), dict(udot=True), {"udot": (self.N, self.nv)}, None if out is None else {"udot": out}, "forward_dynamics")
+        args, keep = self._dynamics_inputs(("tau", "forward_dynamics"), tau, loads, space == RSB_DEVICE)
+        check(self.L.rsb_forward_dynamics(self.handle, *args, _capi.RSB_DYN_CONTACTS if contacts else 0, ptrs[0], space), "rsb_forward_dynamics")
+        return res["udot"]
+
     # -- terrain: heights, height scans and ray tests of every env in one call (rsb_terrain_query.hip) -------------------
     def _terrain_io(self, what, inputs, out_shapes, out):
         """inputs {name: (value, shape)}, out_shapes {name: shape}, out {name: array / tensor or None} -> (space, input pointers, output pointers,
