@@ -324,8 +324,32 @@ __global__ void __launch_bounds__(64) RSB_X_WPE_ATTR rsb_step_kernel(const StepA
   if constexpr (STG != 0) resident_stage<STG, EPW>(ka, blk, 0, ncs);
 #endif
 #include "step_phase_prologue.inc"
+#if RSB_SEAM_CARRY
+  // seam carry (step_spec.h): the state that crosses the boundary between two sub-steps in registers
+  [[maybe_unused]] float sc_q = 0.f, sc_qd = 0.f;      // body lane: the own joint's position and velocity
+  [[maybe_unused]] float sc_qv[7], sc_uv[6];           // every lane: the base's position, quaternion | velocity
+#endif
 #if RSB_RESIDENT
   for (int cs = 0; cs < ncs; ++cs) {
+#endif
+#if RSB_SEAM_CARRY
+  // The registers are filled from LDS once per control step, never per launch: this point follows the prologue (a new launch, a set_state, a set_pd_target) and,
+  // in the resident classes, the epilogue's boundary code (a reset env's state, the next control step's targets) - behind the barrier either of them ends with.
+  // Within the sub-steps of one control step nothing but the update pass writes Q and U.
+  {
+#if RSB_SEAM_BASE
+    float t0[8], t1[8];
+    ldv<2>(Q, t0); ldv<2>(U, t1);
+#endif
+#if RSB_SEAM_JOINTS
+    const float jq = Q[bb + 6], jqd = U[bb + 5];
+    sc_q = isbody ? jq : 0.f; sc_qd = isbody ? jqd : 0.f;
+#endif
+#if RSB_SEAM_BASE
+    RSB_UNROLL for (int i = 0; i < 7; ++i) sc_qv[i] = t0[i];
+    RSB_UNROLL for (int i = 0; i < 6; ++i) sc_uv[i] = t1[i];
+#endif
+  }
 #endif
   for (int sub = 0; sub < nsub; ++sub) {
     RSB_STAMP(0)

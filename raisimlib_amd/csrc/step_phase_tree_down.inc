@@ -5,10 +5,23 @@
 #else
     constexpr bool kBaseMerge = LPE == 16;
 #endif
+#if RSB_SEAM_LOADS
+    // seam carry (step_spec.h): everything the top of the sub-step needs from LDS goes out here as ONE batch, in front of the base arithmetic - which runs from
+    // registers (RSB_SEAM_BASE) and hides the wait - and is collected by one pin behind it.  (The pin of the plain quad form, one empty asm per 16-byte read,
+    // keeps the reads whole but makes every one of them wait for itself: eight dependent round trips of a lone wave.  One asm over all of them waits once.)
+    typedef float sl_f4 __attribute__((ext_vector_type(4)));
+    sl_f4 sl_mv[8];
+    RSB_UNROLL for (int i = 0; i < 8; ++i) sl_mv[i] = *reinterpret_cast<const sl_f4*>(MODELF + bb * RSB_DIM(MODEL_PITCH, L.model_pitch) + 4 * i);
+    float sl_act[5] = {TF[bb + 5], GAIN[2 * bb], GAIN[2 * bb + 1], PT[bb + 6], DTG[bb + 5]};
+#endif
     float R0[9], V0[6], A0[6], I10b[10], Zb[6];
     {
+#if RSB_SEAM_BASE
+      const float* qv = sc_qv; const float* uv = sc_uv;      // (the base's state from registers: loaded at the control step's start, advanced by the update pass)
+#else
       float qv[8], uv[8];
       ldv<2>(Q, qv); ldv<2>(U, uv);
+#endif
       float w = qv[3], x = qv[4], y = qv[5], z = qv[6];
       const float in = 1.0f / sqrtf(w * w + x * x + y * y + z * z);
       w *= in; x *= in; y *= in; z *= in;
@@ -55,7 +68,14 @@
     RSB_UNROLL for (int i = 0; i < 10; ++i) bI10[i] = 0.f;
     {
       float MF[kModelSlot], E9[9], Rb[9], rb[3], Vb[6], Ab[6];
-#if RSB_DOWN_QUADS
+#if RSB_SEAM_LOADS
+      // (the batch issued at the top of the sub-step: one pin keeps the eight 16-byte reads whole, as below, and is the one wait for all of them.
+      //  The last results of the base arithmetic are operands too: they tie the pin - the wait - BEHIND that arithmetic, which the scheduler otherwise sinks below it.)
+      asm volatile("" : "+v"(sl_mv[0]), "+v"(sl_mv[1]), "+v"(sl_mv[2]), "+v"(sl_mv[3]), "+v"(sl_mv[4]), "+v"(sl_mv[5]), "+v"(sl_mv[6]), "+v"(sl_mv[7]),
+                        "+v"(R0[0]), "+v"(R0[4]), "+v"(R0[8]), "+v"(A0[3]), "+v"(A0[4]), "+v"(A0[5]));
+      RSB_UNROLL for (int i = 0; i < 8; ++i) { MF[4 * i] = sl_mv[i].x; MF[4 * i + 1] = sl_mv[i].y; MF[4 * i + 2] = sl_mv[i].z; MF[4 * i + 3] = sl_mv[i].w; }
+      asm volatile("" : "+v"(sl_act[0]), "+v"(sl_act[1]), "+v"(sl_act[2]), "+v"(sl_act[3]), "+v"(sl_act[4]));
+#elif RSB_DOWN_QUADS
       // (the body lanes use every 16-byte chunk of their constants only in part, the axis and the joint's offset on the quads' side now: left to itself the compiler
       //  narrows the eight 16-byte reads to thirteen ds_read2_b32 - the pin keeps them whole)
       RSB_UNROLL for (int i = 0; i < 8; ++i) {
@@ -70,7 +90,11 @@
       const int jt = __float_as_int(MF[3]);
       const float* axis = MF;
       if (isbody) {
+#if RSB_SEAM_JOINTS
+        bqb = sc_q; bqd = sc_qd;      // (the joint's state from registers: loaded at the control step's start, advanced by the update pass)
+#else
         bqb = Q[bb + 6]; bqd = U[bb + 5];
+#endif
         lim_out = (bqb > MF[30]) | (bqb < MF[29]);   // joint outside [q_lower, q_upper]: the joint-limit rows of the collision phase exist only then (rare)
         if (jt == RSB_JOINT_REVOLUTE) {
           float sn, cs;
@@ -229,9 +253,19 @@
 #endif
         // actuation (oracle: actuation_impl): implicit ("stable") PD = position error at q + dt u, plus the joint-space
         // inertia dt (kd + dt kp) added to the armature; an effort-clipped joint is a constant torque source
+#if RSB_SEAM_LOADS
+        // (seam carry: the five scalars are in registers, from the batch at the top of the sub-step)
+        const float* av = sl_act;
+        // (written out as the compiler contracts the expression below where its operands are loads - the damping term a rounded product, the position term fused
+        //  onto it; with the operands in registers it fuses the other product, and the last bit of tau moves)
+        float tau = av[0];
+        const float kpj = av[1], kdj = av[2];
+        tau += fmaf(kpj, fmaf(-dt, bqd, av[3] - bqb), kdj * (av[4] - bqd));
+#else
         float tau = TF[bb + 5];
         const float kpj = GAIN[2 * bb], kdj = GAIN[2 * bb + 1];
         tau += kpj * (PT[bb + 6] - bqb - dt * bqd) + kdj * (DTG[bb + 5] - bqd);
+#endif
         float Bpd = dt * (kdj + dt * kpj);
         const float eff = MF[28];
         if (eff > 0.f && fabsf(tau) > eff) { tau = tau > 0.f ? eff : -eff; Bpd = 0.f; }

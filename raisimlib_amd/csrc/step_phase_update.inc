@@ -19,9 +19,19 @@
         x[i] = sacc * idg[i];
       }
       a0[0] = x[3]; a0[1] = x[4]; a0[2] = x[5]; a0[3] = x[0]; a0[4] = x[1]; a0[5] = x[2];
+#if RSB_SEAM_BASE
+      // seam carry (step_spec.h): the base's q and u are in registers, so lane 0 has nothing to load here; what it stores it also keeps, and the thirteen values
+      // reach the other lanes of the env's row by row_bcast<0> moves behind the region (below): no load and no wait at the top of the next sub-step.
+      // The alternative - every lane evaluating the update itself, which would cost no register more, the registers being the wave's - does not give the same bits:
+      // the solver's row sums leave every lane a sum in an order of its own (step_slip.h, row_sum_f32), so x differs from lane to lane in its last bits, and
+      // the base's state is lane 0's.  Thirteen DPP moves against a store, a barrier and a load.
+      if (s == 0 && !dead) {
+        const float* qv = sc_qv; const float* uv = sc_uv;
+#else
       if (s == 0 && !dead) {
         float qv[8], uv[8];
         ldv<2>(Q, qv); ldv<2>(U, uv);
+#endif
         float un[6], up[6];
         RSB_UNROLL for (int i = 0; i < 6; ++i) { un[i] = uv[i] + x[i]; up[i] = TH ? fmaf(theta, x[i], uv[i]) : un[i]; }   // up: the velocity the positions move with
         // q+ : position, quaternion (world-frame angular velocity); theta = 1: semi-implicit Euler
@@ -32,16 +42,37 @@
         const float sc = (wn > 1e-12f) ? sh / wn : 0.5f * dt;
         const float d0 = chf, d1 = sc * up[3], d2 = sc * up[4], d3 = sc * up[5];
         const float q0 = qv[3], q1 = qv[4], q2 = qv[5], q3 = qv[6];
+#if RSB_SEAM_BASE
+        // (the quaternion product written out as the compiler contracts the four expressions of the #else branch where q is loaded from LDS - the d1 product
+        //  rounded, the others fused onto it one by one; with q in registers it picks other products to round, and the last bits move)
+        float r0 = fmaf(-d3, q3, fmaf(-d2, q2, fmaf(d0, q0, -(d1 * q1))));
+        float r1 = fmaf(-d3, q2, fmaf(d2, q3, fmaf(d0, q1, d1 * q0)));
+        float r2 = fmaf(d3, q1, fmaf(d2, q0, fmaf(d0, q2, -(d1 * q3))));
+        float r3 = fmaf(d3, q0, fmaf(-d2, q1, fmaf(d0, q3, d1 * q2)));
+#else
         float r0 = d0 * q0 - d1 * q1 - d2 * q2 - d3 * q3;
         float r1 = d0 * q1 + d1 * q0 + d2 * q3 - d3 * q2;
         float r2 = d0 * q2 - d1 * q3 + d2 * q0 + d3 * q1;
         float r3 = d0 * q3 + d1 * q2 - d2 * q1 + d3 * q0;
+#endif
         const float in = 1.0f / sqrtf(r0 * r0 + r1 * r1 + r2 * r2 + r3 * r3);
         // joint entries of Q / U are owned by the body lanes: write only the base entries
+#if RSB_SEAM_BASE
+        const float qn[7] = {qv[0] + dt * up[0], qv[1] + dt * up[1], qv[2] + dt * up[2], r0 * in, r1 * in, r2 * in, r3 * in};
+        RSB_UNROLL for (int i = 0; i < 7; ++i) Q[i] = qn[i];
+        RSB_UNROLL for (int i = 0; i < 6; ++i) U[i] = un[i];
+        RSB_UNROLL for (int i = 0; i < 7; ++i) sc_qv[i] = qn[i];      // (a dead env keeps its old values, as its rows of Q and U do)
+        RSB_UNROLL for (int i = 0; i < 6; ++i) sc_uv[i] = un[i];
+#else
         Q[0] = qv[0] + dt * up[0]; Q[1] = qv[1] + dt * up[1]; Q[2] = qv[2] + dt * up[2];
         Q[3] = r0 * in; Q[4] = r1 * in; Q[5] = r2 * in; Q[6] = r3 * in;
         RSB_UNROLL for (int i = 0; i < 6; ++i) U[i] = un[i];
+#endif
       }
+#if RSB_SEAM_BASE
+      RSB_UNROLL for (int i = 0; i < 7; ++i) sc_qv[i] = row_bcast<0>(sc_qv[i]);      // (lane 0's new - or, of a dead env, old - values to the sixteen lanes of the env)
+      RSB_UNROLL for (int i = 0; i < 6; ++i) sc_uv[i] = row_bcast<0>(sc_uv[i]);
+#endif
     }
     // joints, level by level from the base: a body takes its parent's delta-velocity from LDS (the A slot of the parent's
     // BODY entry, free since the down pass), resolves its own joint and leaves its own for its children
@@ -71,15 +102,29 @@
         RSB_UNROLL for (int i = 0; i < 6; ++i)
           ap[i] = (lv == 1) ? a0[i] : __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(an[i]), 0x111, 0xf, 0xf, true));   // row_shr:1
         if (mylev == lv) {
-          const float xk = brsD * WB[bb + 5] - dot6(bUD, ap);
+          const float xk = brsD * WB[bb + 5] - dot6(bUD, ap);   // WB = W_b plus the contact contributions scattered by the contact lanes
           const float un = bqd + xk;
+#if RSB_SEAM_JOINTS
+          const float qn = bqb + dt * (TH ? fmaf(theta, xk, bqd) : un);
+          if (!dead) {
+            U[bb + 5] = un;
+            Q[bb + 6] = qn;
+            sc_qd = un; sc_q = qn;      // (seam carry: what the lane stored is the next sub-step's bqd, bqb; a dead env's lanes keep their old ones)
+          }
+#else
           if (!dead) {
             U[bb + 5] = un;
             Q[bb + 6] = bqb + dt * (TH ? fmaf(theta, xk, bqd) : un);
           }
+#endif
           RSB_UNROLL for (int i = 0; i < 6; ++i) an[i] = ap[i] + bS[i] * xk;
         }
       }
+      // (seam carry: with the base's and the joints' state crossing in registers, the top of the next sub-step no longer reads what this pass stored.  The barrier
+      //  stays: behind the LAST sub-step the epilogue reads Q and U - and, of a wave without contacts, the cleared warm table - across lanes; and in such a wave, where
+      //  no barrier follows the up pass, it stands between the base gather's reads of UPS slot 0 and the next down pass's staging stores to the same floats.  A form
+      //  with this barrier moved onto the down pass's wait for the MODELF batch was built and gave the same bits; it needs a second barrier behind the sub-step loop
+      //  for the epilogue, and whether it is any faster was not measured against this form: DESIGN.md section 11.)
       __syncthreads();
     }
 #else

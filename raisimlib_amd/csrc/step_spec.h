@@ -49,6 +49,39 @@
 #define RSB_DOWN_QUADS 0
 #endif
 
+// Seam carry, for the same worlds and code objects (the classes that run both quad forms): what one sub-step's update pass leaves for the next sub-step's down pass
+// stays in registers instead of making a round trip through LDS (step_phase_tree_down.inc, step_phase_update.inc, step_kernel.h).  Three parts, each with a switch
+// of its own for an A/B:
+//   RSB_SEAM_JOINTS  a body lane keeps its joint's q and qd across the seam (loaded once per control step, in front of the sub-step loop)
+//   RSB_SEAM_BASE    the base's q (7) and u (6) stay in registers: lane 0 updates them from its registers, thirteen row_bcast<0> moves hand them to the env's row
+//   RSB_SEAM_LOADS   the lane's MODELF row and the actuation's five scalars (feed-forward torque, kp, kd, target, target velocity) are fetched as ONE batch with one
+//                    wait, issued in front of the base arithmetic
+// (Two more parts were built and measured, and are not here: the five scalars held in registers over a control step, and the update pass's entry of W_b read once
+//  instead of per level - DESIGN.md section 9.)
+// With JOINTS and BASE nothing at the top of a sub-step reads what the update pass wrote; the barrier that closes the update pass stays all the same
+// (step_phase_update.inc says what it still orders).  The stores to Q and U stay: joint limits, contact columns, the epilogue and the host read them.
+// -DRSB_X_NO_SEAM_CARRY compiles the code as it was: same results bit for bit (tests/test_gpu_seam_carry.py).
+#if RSB_DOWN_QUADS && !defined(RSB_X_NO_SEAM_CARRY)
+#define RSB_SEAM_CARRY 1
+#else
+#define RSB_SEAM_CARRY 0
+#endif
+#if RSB_SEAM_CARRY && !defined(RSB_X_NO_SEAM_JOINTS)
+#define RSB_SEAM_JOINTS 1
+#else
+#define RSB_SEAM_JOINTS 0
+#endif
+#if RSB_SEAM_CARRY && !defined(RSB_X_NO_SEAM_BASE)
+#define RSB_SEAM_BASE 1
+#else
+#define RSB_SEAM_BASE 0
+#endif
+#if RSB_SEAM_CARRY && !defined(RSB_X_NO_SEAM_LOADS)
+#define RSB_SEAM_LOADS 1
+#else
+#define RSB_SEAM_LOADS 0
+#endif
+
 namespace rsbk {
 #define RSB_SPEC_COUNT_ONE(NAME, expr) +1
 constexpr int kSpecFields = 0 RSB_SPEC_FIELDS(RSB_SPEC_COUNT_ONE);
