@@ -318,7 +318,15 @@ __global__ void __launch_bounds__(64) RSB_X_WPE_ATTR rsb_step_kernel(const StepA
     __syncthreads();
   }
 #if RSB_RESIDENT
+#if RSB_SPEC_CONSTS
+  // (pinned: with the settings' SGPRs free the register allocator stops holding the count and re-reads it from the kernel arguments in every control step's
+  //  epilogue instead - a scalar-cache round trip where a register copy does.  The asm waits for this one load, once per launch)
+  int ncs_pin = a.res_steps;
+  asm volatile("" : "+s"(ncs_pin));
+  const int ncs = ncs_pin;
+#else
   const int ncs = a.res_steps;   // control steps of this launch
+#endif
   // closed loop: pass 0 of the action stage - the actions of the first control step from the observation the host left in env_ob - before the
   // prologue reads the action rows
   if constexpr (STG != 0) resident_stage<STG, EPW>(ka, blk, 0, ncs);
@@ -362,7 +370,7 @@ __global__ void __launch_bounds__(64) RSB_X_WPE_ATTR rsb_step_kernel(const StepA
     float wlam[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // base part of sum_c W_c lam_c (left by the solver on the lanes of the env's first row)
     if (ncw > 0) {
       RSB_ARGS(aw);
-      const float erp = aw.erp;
+      const float erp = RSB_DIM_F32(ERP, aw.erp);
 #include "step_phase_columns.inc"
 #include "step_phase_delassus.inc"
 #include "step_phase_solver.inc"

@@ -67,13 +67,13 @@
             if (jp && lo != hi) { gidc = (gidc == hi) ? lo : gidc; gidb = (gidb == hi) ? lo : gidb; }
           }
         }
-        float mu = (isc && mycol < ncol) ? COLT[kColSlot * mycol + 5] : ag.mu;
+        float mu = (isc && mycol < ncol) ? COLT[kColSlot * mycol + 5] : RSB_DIM_F32(MU, ag.mu);
         if constexpr (HM2) { if (isc && (mycol & kExtra)) mu = COLT[kColSlot * (mycol & 0xffff) + 5]; }
         if (mycol & kSelfA) mu = SELFT[4 * s];    // material pair of the two primitives
         const float mu2 = mu * mu;
-        const float alpha_init = ag.alpha_init, alpha_min = ag.alpha_min, alpha_decay = ag.alpha_decay, threshold = ag.threshold;
-        const float stall_factor = ag.stall_factor;
-        const int max_iter = ag.max_iter, section_rounds = RSB_DIM(SECTION_ROUNDS, ag.section_rounds), stall_window = RSB_DIM(STALL_WINDOW, ag.stall_window);
+        const float alpha_init = RSB_DIM_F32(ALPHA_INIT, ag.alpha_init), alpha_min = RSB_DIM_F32(ALPHA_MIN, ag.alpha_min), alpha_decay = RSB_DIM_F32(ALPHA_DECAY, ag.alpha_decay);
+        const float threshold = RSB_DIM_F32(THRESHOLD, ag.threshold), stall_factor = RSB_DIM_F32(STALL_FACTOR, ag.stall_factor);
+        const int max_iter = RSB_DIM_INT(MAX_ITER, ag.max_iter), section_rounds = RSB_DIM(SECTION_ROUNDS, ag.section_rounds), stall_window = RSB_DIM(STALL_WINDOW, ag.stall_window);
         const int freeze_after = RSB_DIM(FREEZE_AFTER, ag.freeze_after), refine = RSB_DIM(REFINE, ag.refine), multi_fa = RSB_DIM(MULTI_FA, ag.multi_freeze_after);
         // per-solve constants of the own contact: den(d) = a0 + a1 x + a2 y; n01.. hold mu * G_tt (see slip_prepare)
         SlipCoef sc;

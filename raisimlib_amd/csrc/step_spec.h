@@ -18,12 +18,38 @@
   X(EARLY_TERM, (a.early_term != 0)) X(SECTION_ROUNDS, a.section_rounds) X(STALL_WINDOW, a.stall_window) X(FREEZE_AFTER, a.freeze_after) \
   X(REFINE, a.refine) X(MULTI_FA, a.multi_freeze_after) X(MULTI_DEPTH, a.multi_depth) X(MULTI_LIGHT, a.multi_light)                    \
   X(MULTI_SW, a.multi_stall_window) X(CHAIN, (a.chain != 0)) X(MODEL_PITCH, a.L.model_pitch) \
-  X(UP_QUADS, (a.chain == 2))
+  X(UP_QUADS, (a.chain == 2)) \
+  X(MU, rsbk::spec_bits(a.mu)) X(ERP, rsbk::spec_bits(a.erp)) X(ALPHA_INIT, rsbk::spec_bits(a.alpha_init)) X(ALPHA_MIN, rsbk::spec_bits(a.alpha_min)) \
+  X(ALPHA_DECAY, rsbk::spec_bits(a.alpha_decay)) X(THRESHOLD, rsbk::spec_bits(a.threshold)) X(STALL_FACTOR, rsbk::spec_bits(a.stall_factor)) \
+  X(MAX_ITER, a.max_iter)
 
 #ifdef RSB_SPECIALIZED
 #define RSB_DIM(NAME, expr) (RSB_SPEC_##NAME)
 #else
 #define RSB_DIM(NAME, expr) (expr)
+#endif
+
+// The contact solve's scalar settings (the fields from MU on): the default friction coefficient, ERP, the solver's relaxation (alpha_init, alpha_min, alpha_decay),
+// its convergence threshold, stagnation factor and sweep limit.  They are fixed for a world's life in real use, and the sub-step loop read every one of them from
+// the kernel arguments in every sub-step, at the solver's entry and in the contact columns: a scalar-cache round trip each, collected by an lgkmcnt(0) that also
+// drains the LDS batch in flight around it (the coupling blocks, the FACT reads), and a live SGPR across the solve.  A float enters the key as its BIT PATTERN,
+// written as a signed decimal integer (-0, denormals and NaN payloads are keys of their own); the kernel turns it back with a constexpr bit cast, so the value is a
+// literal operand.  A world with any other value has another key: it runs its ahead-of-time class, or a code object of its own (rsb_spec.hip).
+// -DRSB_X_NO_SPEC_CONSTS (RSB_SPEC_EXTRA_DEFS) reads the fields from the arguments again: same results bit for bit (tests/test_gpu_spec_consts.py).
+// (The time step with gravity, and the ground height, were key fields in a first form and are not: they measured nothing, and their literals moved bits at three
+//  sites that then had to be kept opaque - DESIGN.md sections 5.3 and 9.)
+namespace rsbk {
+constexpr int spec_bits(float f) { return __builtin_bit_cast(int, f); }
+constexpr float spec_f32(int bits) { return __builtin_bit_cast(float, bits); }
+}  // namespace rsbk
+#if defined(RSB_SPECIALIZED) && !defined(RSB_X_NO_SPEC_CONSTS)
+#define RSB_SPEC_CONSTS 1
+#define RSB_DIM_F32(NAME, expr) (rsbk::spec_f32((int)(RSB_SPEC_##NAME)))
+#define RSB_DIM_INT(NAME, expr) ((int)(RSB_SPEC_##NAME))
+#else
+#define RSB_SPEC_CONSTS 0
+#define RSB_DIM_F32(NAME, expr) (expr)
+#define RSB_DIM_INT(NAME, expr) (expr)
 #endif
 
 // Quad form of the up pass's level loop (step_phase_tree_up.inc): four lanes per body instead of one, in the specialised code objects of worlds whose
