@@ -4,9 +4,12 @@
 // the host [RECALL], and the centroidal momentum matrix, for all N envs in one call, from d_gc / d_gv on the world's stream.  Nothing here is shared
 // with the step kernel: two short kernels of their own, called between two control steps.
 //
-// Both kernels give a workgroup epb = 256 / nb CONSECUTIVE envs and one lane per (env, body).  A lane walks its body's support chain
-// (walk_chain, frames_chain.h: the running transform and velocity in registers), so it knows R_i, p_i, omega_i, v_i of its body; the extra body
-// constants (centre of mass, inertia, armature: 17-26 of DevModel::bodyf) come from an LDS table of their own, not from the walk's rows.
+// Both kernels give a workgroup epb = 256 / nb CONSECUTIVE envs and one lane per (env, body) (EnvBlock).  A lane walks its body's support chain
+// (walk_chain: the running transform and velocity in registers), so it knows R_i, p_i, omega_i, v_i of its body; the extra body constants (centre
+// of mass, inertia, armature: 17-26 of DevModel::bodyf) come from an LDS table of their own (stage_xtra), not from the walk's rows.  The walk, the
+// tables and the staging of the RSB_HOST forms are those of all batched queries (frames_chain.h).  centroidal_matrix_kernel keeps its own
+// prologue, inertia block and subtree loop, not EnvBlock / inertia_about_o / subtree_sum: with them its instructions come in another order, 0.1 us
+// slower on the Atlas-like model (profiles/query_common_ab.txt).
 // Everything that is summed over bodies - first moments, angular momentum, inertia - is taken about the env's BASE ORIGIN o = p_0, never about the
 // world origin: an env standing 50 m away keeps all its bits for what happens inside the robot.
 //     r_i = (p_i - o) + R_i com_i      v_ci = v_i + omega_i x R_i com_i      I_w,i = R_i I_i R_i^T
@@ -32,26 +35,9 @@
 namespace rsbw {
 namespace {
 
-constexpr int kXtra = 11;      // floats per body in the extra table (odd pitch): com 0-2, inertia xx xy xz yy yz zz 3-8, armature 9
 constexpr int kPart = 11;      // centroidal_kernel: ten partials per lane, odd pitch
 constexpr int kRec = 17;       // centroidal_matrix_kernel, per lane: m 0, m r 1-3, inertia about o 4-9, a 10-12, s 13-15, revolute 16
 constexpr int kComp = 11;      // ... and per (env, body) composite: m* 0, h* 1-3, I* 4-9
-
-struct Vec3 { float x, y, z; };
-
-__device__ __forceinline__ void stage_xtra(const DevModel& m, float* xtra) {
-  for (int k = threadIdx.x; k < m.nb * kXtra; k += kThreads) {
-    const int b = k / kXtra, c = k - b * kXtra;
-    xtra[k] = c < 10 ? m.bodyf[b][17 + c] : 0.f;
-  }
-}
-
-// I x for the symmetric I = (xx xy xz yy yz zz)
-__device__ __forceinline__ void sym3_vec(const float* I, const float* x, float* o) {
-  o[0] = I[0] * x[0] + I[1] * x[1] + I[2] * x[2];
-  o[1] = I[1] * x[0] + I[3] * x[1] + I[4] * x[2];
-  o[2] = I[2] * x[0] + I[4] * x[1] + I[5] * x[2];
-}
 
 __global__ __launch_bounds__(kThreads) void centroidal_kernel(const DevModel* __restrict__ model, const float* __restrict__ gc, const float* __restrict__ gv, int N,
                                                               float total_mass, const Vec3 g, float* __restrict__ com, float* __restrict__ com_vel,
@@ -65,22 +51,20 @@ __global__ __launch_bounds__(kThreads) void centroidal_kernel(const DevModel* __
   stage_rows(m, rows);
   stage_xtra(m, xtra);
   __syncthreads();
-  const int nb = m.nb, epb = kThreads / nb;
-  const long long env0 = (long long)blockIdx.x * epb;
-  const int here = (int)min((long long)epb, (long long)N - env0);
-  const int el = threadIdx.x / nb, body = threadIdx.x - el * nb;
+  const int nb = m.nb;
+  const auto [env0, here, el, body] = env_block(nb, N);
   if (el < here) {
     const float* q = gc + (size_t)(env0 + el) * m.nq;
     const float* u = gv + (size_t)(env0 + el) * m.nv;
     Chain c;
-    walk_chain(m, rows, q, u, true, body, c, [](int, int, const float*, const float*, bool) {});
+    walk_chain<false>(m, rows, q, u, nullptr, true, body, c, NoJoint{});
     const float* x = xtra + body * kXtra;
     const float mass = rows[body * kRow + 7];
     float rc[3], wr[3], r[3], vc[3], wb[3], Iwb[3], Iw[3], rv[3];
     mat3_vec(c.R, x, rc);
     cross3(c.w, rc, wr);
     for (int k = 0; k < 3; ++k) { r[k] = (c.p[k] - q[k]) + rc[k]; vc[k] = c.v[k] + wr[k]; }
-    for (int k = 0; k < 3; ++k) wb[k] = c.R[k] * c.w[0] + c.R[3 + k] * c.w[1] + c.R[6 + k] * c.w[2];      // R^T omega
+    for (int k = 0; k < 3; ++k) wb[k] = c.R[k] * c.w[0] + c.R[3 + k] * c.w[1] + c.R[6 + k] * c.w[2];      // R^T omega (not mat3t_vec: inlined here it contracts differently and the bits move)
     sym3_vec(x + 3, wb, Iwb);
     mat3_vec(c.R, Iwb, Iw);
     cross3(r, vc, rv);
@@ -142,7 +126,7 @@ __global__ __launch_bounds__(kThreads) void centroidal_matrix_kernel(const DevMo
     const float* q = gc + (size_t)(env0 + el) * m.nq;
     float a[3] = {0.f, 0.f, 0.f}, sj[3] = {0.f, 0.f, 0.f}, rev = 0.f;
     Chain c;
-    walk_chain(m, rows, q, nullptr, false, body, c, [&](int, int, const float* ai, const float* pi, bool revolute) {      // the last call is the body's own joint
+    walk_chain<false>(m, rows, q, nullptr, nullptr, false, body, c, [&](int, int, const float* ai, const float* pi, bool revolute) {      // the last call is the body's own joint
       for (int k = 0; k < 3; ++k) { a[k] = ai[k]; sj[k] = pi[k] - q[k]; }
       rev = revolute ? 1.f : 0.f;
     });
@@ -251,48 +235,36 @@ int rsb_get_centroidal(rsb_world* w, float* com, float* com_vel, float* lin_mom,
   float* host[6] = {com, com_vel, lin_mom, ang_mom, kinetic, potential};
   bool any = false;
   for (float* p : host) any = any || p;
-  if (!any) { rsb::set_error(std::string(who) + ": every output is NULL"); return RSB_E_INVALID; }
+  if (!any) return invalid(who, "every output is NULL");
   float total = 0.f;
   st = check_mass(w, who, &total); if (st != RSB_OK) return st;
   HIP_TRY(hipSetDevice(w->device));
-  const size_t N = (size_t)w->N;
-  float* dev[6] = {com, com_vel, lin_mom, ang_mom, kinetic, potential};
+  float* dev[6];
   const size_t width[6] = {3, 3, 3, 3, 1, 1};
-  if (space == RSB_HOST) {
-    st = staging(w, N * 14); if (st != RSB_OK) return st;
-    size_t off = 0;
-    for (int k = 0; k < 6; ++k) if (host[k]) { dev[k] = w->d_frames_io + off; off += N * width[k]; }
-  }
-  const int epb = kThreads / w->blob.nb;
-  const Vec3 g = {(float)w->gravity[0], (float)w->gravity[1], (float)w->gravity[2]};
-  hipLaunchKernelGGL(centroidal_kernel, dim3((unsigned)((N + epb - 1) / epb)), dim3(kThreads), 0, stream_of(w), (const DevModel*)w->d_model, (const float*)w->d_gc,
-                     (const float*)w->d_gv, w->N, total, g, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5]);
+  Staged io(w, space);
+  for (int k = 0; k < 6; ++k) io.out(dev[k], host[k], (size_t)w->N * width[k]);
+  st = io.begin(); if (st != RSB_OK) return st;
+  hipLaunchKernelGGL(centroidal_kernel, dim3(env_blocks(w)), dim3(kThreads), 0, stream_of(w), (const DevModel*)w->d_model, (const float*)w->d_gc,
+                     (const float*)w->d_gv, w->N, total, gravity_of(w), dev[0], dev[1], dev[2], dev[3], dev[4], dev[5]);
   HIP_TRY(hipGetLastError());
-  if (space == RSB_HOST)
-    for (int k = 0; k < 6; ++k)
-      if (host[k]) { st = copy_out(w, host[k], dev[k], N * width[k] * sizeof(float), RSB_HOST); if (st != RSB_OK) return st; }
-  return RSB_OK;
+  return io.end();
 }
 
 int rsb_get_centroidal_momentum_matrix(rsb_world* w, float* A, int space) {
   const char* who = "rsb_get_centroidal_momentum_matrix";
   int st = check_world(w, who, space); if (st != RSB_OK) return st;
-  if (!A) { rsb::set_error(std::string(who) + ": the output is NULL"); return RSB_E_INVALID; }
+  if (!A) return invalid(who, "the output is NULL");
   float total = 0.f;
   st = check_mass(w, who, &total); if (st != RSB_OK) return st;
   HIP_TRY(hipSetDevice(w->device));
-  const size_t N = (size_t)w->N, floats = N * 6 * w->blob.nv;
-  float* dA = A;
-  if (space == RSB_HOST) {
-    st = staging(w, floats); if (st != RSB_OK) return st;
-    dA = w->d_frames_io;
-  }
-  const int epb = kThreads / w->blob.nb;
-  hipLaunchKernelGGL(centroidal_matrix_kernel, dim3((unsigned)((N + epb - 1) / epb)), dim3(kThreads), 0, stream_of(w), (const DevModel*)w->d_model,
-                     (const float*)w->d_gc, w->N, total, dA);
+  float* dA;
+  Staged io(w, space);
+  io.out(dA, A, (size_t)w->N * 6 * w->blob.nv);
+  st = io.begin(); if (st != RSB_OK) return st;
+  hipLaunchKernelGGL(centroidal_matrix_kernel, dim3(env_blocks(w)), dim3(kThreads), 0, stream_of(w), (const DevModel*)w->d_model, (const float*)w->d_gc, w->N,
+                     total, dA);
   HIP_TRY(hipGetLastError());
-  if (space == RSB_HOST) { st = copy_out(w, A, dA, floats * sizeof(float), RSB_HOST); if (st != RSB_OK) return st; }
-  return RSB_OK;
+  return io.end();
 }
 
 }  // extern "C"

@@ -5,12 +5,10 @@
 // shared with the step kernel or with the one-thread-per-env query kernel: two kernels of their own, called between two control steps, that write
 // nothing but their outputs.
 //
-// Both kernels give a workgroup epb = 256 / nb CONSECUTIVE envs and one lane per (env, body), as rsb_centroidal.hip does.  A lane walks its body's
-// support chain root -> body (walk_dyn: frames_chain.h's walk with the parent's velocity kept and, for the inverse dynamics, the accelerations
-// carried along) with everything in registers: no per-body arrays, no scratch, no cross-lane traffic.
-//     revolute    alpha_i = alpha_p + a_i qdd_i + omega_p x a_i qd_i        acc_i = acc_p + alpha_p x d + omega_p x (omega_p x d)
-//     prismatic   alpha_i = alpha_p                                         acc_i = ... + 2 omega_p x a_i qd_i + a_i qdd_i          d = p_i - p_p
-// (acc: the classical acceleration of the body's origin, d/dt of its world velocity - what udot[0:3] is for the base).
+// Both kernels give a workgroup epb = 256 / nb CONSECUTIVE envs and one lane per (env, body) (EnvBlock), as rsb_centroidal.hip does.  A lane walks
+// its body's support chain root -> body (walk_chain, the one walk of all batched queries: it keeps the parent's velocity and, for the inverse
+// dynamics, carries the accelerations along) with everything in registers: no per-body arrays, no scratch, no cross-lane traffic.  The walk, the
+// model tables, the inertia about o, the subtree sum and the staging of the RSB_HOST forms are shared with the other queries (frames_chain.h).
 // Every moment is taken about the env's BASE ORIGIN o = p_0, never about the world origin: an env standing 50 m away keeps all its bits.
 // External loads and contact records are added by the lane whose body they act on, in ascending index: the frame list first, then the env's contact
 // records.  No atomics anywhere; every sum has a fixed order.
@@ -36,109 +34,19 @@
 namespace rsbw {
 namespace {
 
-constexpr int kXtra = 11;      // floats per body in the extra table (odd pitch): com 0-2, inertia xx xy xz yy yz zz 3-8, armature 9
 constexpr int kWr = 15;        // rnea_kernel, per lane: f 0-2, n about o 3-5, a 6-8, s 9-11, joint type 12 (0 base, 1 revolute, 2 prismatic), qdd 13
 constexpr int kOut = 7;        // ... and per (env, body) result: joint force 0-2, joint torque 3-5, tau 6
 constexpr int kArt = 27;       // aba_kernel, per lane: J 0-5, H 6-14, M 15-20, bias force 21-26
 constexpr int kAcc = 7;        // ... spatial acceleration (angular 0-2, linear 3-5)
 constexpr int kRowsOut = 1536; // ... udot rows of the block: epb * (nb + 5) <= 256 + 5 * 256
 
-struct Vec3 { float x, y, z; };
-
 // what acts on the bodies besides gravity: F frames with force / torque [N,F,3] (either may be null), the resident contact list (null: not asked for)
 struct Loads { const float* force; const float* torque; const rsb_contact* contacts; const int32_t* count; int F, kmax; float inv_dt; };
 
-// a body at the end of its chain walk; wp, vp, pp: the parent's angular velocity, velocity and position (the base's own for body 0)
-struct Body { float R[9], p[3], w[3], v[3], al[3], ac[3], a[3], wp[3], vp[3], pp[3], qd, qdd; int type; };
-
-__device__ __forceinline__ void stage_xtra(const DevModel& m, float* xtra) {
-  for (int k = threadIdx.x; k < m.nb * kXtra; k += kThreads) {
-    const int b = k / kXtra, c = k - b * kXtra;
-    xtra[k] = c < 10 ? m.bodyf[b][17 + c] : 0.f;
-  }
-}
-
-// I x for the symmetric I = (xx xy xz yy yz zz)
-__device__ __forceinline__ void sym3_vec(const float* I, const float* x, float* o) {
-  o[0] = I[0] * x[0] + I[1] * x[1] + I[2] * x[2];
-  o[1] = I[1] * x[0] + I[3] * x[1] + I[4] * x[2];
-  o[2] = I[2] * x[0] + I[4] * x[1] + I[5] * x[2];
-}
-// A^T x for the row-major 3 x 3 A
-__device__ __forceinline__ void mat3t_vec(const float* A, const float* x, float* o) {
-  for (int c = 0; c < 3; ++c) o[c] = A[c] * x[0] + A[3 + c] * x[1] + A[6 + c] * x[2];
-}
 // 1 / x: the hardware's approximation and one Newton step
 __device__ __forceinline__ float recip(float x) {
   const float r = __builtin_amdgcn_rcpf(x);
   return fmaf(fmaf(-x, r, 1.f), r, r);
-}
-
-// frames_chain.h's walk_chain (the same arithmetic for R and p), keeping the parent's velocity and, with ACC, carrying the accelerations.
-// ud may be null (zeros).  A fixed base neither moves nor accelerates: its rows of u and ud are not read.
-template <bool ACC>
-__device__ __forceinline__ void walk_dyn(const DevModel& m, const float* rows, const float* q, const float* u, const float* ud, int body, Body& b) {
-  {
-    float w = q[3], x = q[4], y = q[5], z = q[6];
-    const float in = 1.0f / sqrtf(w * w + x * x + y * y + z * z);
-    w *= in; x *= in; y *= in; z *= in;
-    b.R[0] = 1 - 2 * (y * y + z * z); b.R[1] = 2 * (x * y - w * z);     b.R[2] = 2 * (x * z + w * y);
-    b.R[3] = 2 * (x * y + w * z);     b.R[4] = 1 - 2 * (x * x + z * z); b.R[5] = 2 * (y * z - w * x);
-    b.R[6] = 2 * (x * z - w * y);     b.R[7] = 2 * (y * z + w * x);     b.R[8] = 1 - 2 * (x * x + y * y);
-    const bool moves = !m.fixed_base;
-    for (int k = 0; k < 3; ++k) {
-      b.p[k] = q[k]; b.v[k] = moves ? u[k] : 0.f; b.w[k] = moves ? u[3 + k] : 0.f;
-      b.ac[k] = (ACC && moves && ud) ? ud[k] : 0.f; b.al[k] = (ACC && moves && ud) ? ud[3 + k] : 0.f;
-      b.a[k] = 0.f; b.wp[k] = b.w[k]; b.vp[k] = b.v[k]; b.pp[k] = b.p[k];
-    }
-    b.qd = 0.f; b.qdd = 0.f; b.type = 0;
-  }
-  const int lv = m.level[body];
-  const int* anc = m.anc + body * m.depth;
-  for (int l = 1; l <= lv; ++l) {
-    const int i = anc[l];
-    const float* row = rows + i * kRow;
-    const bool revolute = __float_as_int(row[3]) == RSB_JOINT_REVOLUTE;
-    const float ax[3] = {row[0], row[1], row[2]}, pt[3] = {row[4], row[5], row[6]};
-    const float qi = q[6 + i], qd = u[5 + i], qdd = (ACC && ud) ? ud[5 + i] : 0.f;
-    float E[9], Rn[9], d[3], a[3];
-    if (revolute) {
-      float sn, cs, Rq[9];
-      sincosf(qi, &sn, &cs);
-      const float t = 1.f - cs;
-      Rq[0] = cs + ax[0] * ax[0] * t;         Rq[1] = ax[0] * ax[1] * t - ax[2] * sn; Rq[2] = ax[0] * ax[2] * t + ax[1] * sn;
-      Rq[3] = ax[1] * ax[0] * t + ax[2] * sn; Rq[4] = cs + ax[1] * ax[1] * t;         Rq[5] = ax[1] * ax[2] * t - ax[0] * sn;
-      Rq[6] = ax[2] * ax[0] * t - ax[1] * sn; Rq[7] = ax[2] * ax[1] * t + ax[0] * sn; Rq[8] = cs + ax[2] * ax[2] * t;
-      mat3_mul(row + 8, Rq, E);
-    } else {
-      for (int k = 0; k < 9; ++k) E[k] = row[8 + k];
-    }
-    mat3_mul(b.R, E, Rn);
-    mat3_vec(b.R, pt, d);
-    mat3_vec(Rn, ax, a);
-    if (!revolute) for (int k = 0; k < 3; ++k) d[k] += a[k] * qi;
-    float wd[3], wa[3];
-    cross3(b.w, d, wd);
-    cross3(b.w, a, wa);
-    for (int k = 0; k < 3; ++k) { b.wp[k] = b.w[k]; b.vp[k] = b.v[k]; b.pp[k] = b.p[k]; }
-    if (ACC) {
-      float ad[3], wwd[3];
-      cross3(b.al, d, ad);
-      cross3(b.w, wd, wwd);
-      for (int k = 0; k < 3; ++k) {
-        b.ac[k] += ad[k] + wwd[k] + (revolute ? 0.f : 2.f * wa[k] * qd + a[k] * qdd);
-        b.al[k] += revolute ? a[k] * qdd + wa[k] * qd : 0.f;
-      }
-    }
-    for (int k = 0; k < 3; ++k) {
-      b.v[k] += wd[k] + (revolute ? 0.f : a[k] * qd);
-      b.w[k] += revolute ? a[k] * qd : 0.f;
-      b.p[k] += d[k];
-      b.a[k] = a[k];
-    }
-    for (int k = 0; k < 9; ++k) b.R[k] = Rn[k];
-    b.qd = qd; b.qdd = qdd; b.type = revolute ? 1 : 2;
-  }
 }
 
 // the external force on `body` and its moment about o: the frames of the list that sit on the body, then the env's contact records on it, ascending
@@ -179,17 +87,15 @@ __global__ __launch_bounds__(kThreads) void rnea_kernel(const DevModel* __restri
   stage_rows(m, rows);
   stage_xtra(m, xtra);
   __syncthreads();
-  const int nb = m.nb, epb = kThreads / nb, depth = m.depth, nv = m.nv;
-  const long long env0 = (long long)blockIdx.x * epb;
-  const int here = (int)min((long long)epb, (long long)N - env0);
-  const int el = threadIdx.x / nb, body = threadIdx.x - el * nb;
+  const int nb = m.nb, depth = m.depth, nv = m.nv;
+  const auto [env0, here, el, body] = env_block(nb, N);
   if (el < here) {
     const long long env = env0 + el;
     const float* q = gc + (size_t)env * m.nq;
     const float* u = gv + (size_t)env * nv;
     const float* ud = udot ? udot + (size_t)env * nv : nullptr;
-    Body b;
-    walk_dyn<true>(m, rows, q, u, ud, body, b);
+    Chain b;
+    walk_chain<true>(m, rows, q, u, ud, true, body, b, NoJoint{});
     const float* x = xtra + body * kXtra;
     const float mass = rows[body * kRow + 7];
     const float gvec[3] = {g.x, g.y, g.z};
@@ -221,14 +127,9 @@ __global__ __launch_bounds__(kThreads) void rnea_kernel(const DevModel* __restri
   }
   __syncthreads();
   if (el < here) {      // the wrench joint j carries: the sum over the subtree below this lane's body
-    const int lj = m.level[body];
     const float* s = rec + el * nb * kWr;
     float acc[6];
-    for (int k = 0; k < 6; ++k) acc[k] = 0.f;
-    for (int i = body; i < nb; ++i) {      // (a subtree's bodies are numbered from its root up: parent[i] < i)
-      if (m.anc[i * depth + lj] != body) continue;
-      for (int k = 0; k < 6; ++k) acc[k] += s[i * kWr + k];
-    }
+    subtree_sum<6>(m, nb, depth, s, kWr, body, acc);
     const float* me = s + body * kWr;
     float sf[3];
     cross3(me + 9, acc, sf);
@@ -316,10 +217,8 @@ __global__ __launch_bounds__(kThreads) void aba_kernel(const DevModel* __restric
   stage_rows(m, rows);
   stage_xtra(m, xtra);
   __syncthreads();
-  const int nb = m.nb, epb = kThreads / nb, depth = m.depth, nv = m.nv;
-  const long long env0 = (long long)blockIdx.x * epb;
-  const int here = (int)min((long long)epb, (long long)N - env0);
-  const int el = threadIdx.x / nb, body = threadIdx.x - el * nb;
+  const int nb = m.nb, depth = m.depth, nv = m.nv;
+  const auto [env0, here, el, body] = env_block(nb, N);
   const bool active = el < here;
   const int level = active ? m.level[body] : -1;
   const float gvec[3] = {g.x, g.y, g.z};
@@ -333,11 +232,11 @@ __global__ __launch_bounds__(kThreads) void aba_kernel(const DevModel* __restric
     const float* q = gc + (size_t)env * m.nq;
     const float* u = gv + (size_t)env * nv;
     trow = tau + (size_t)env * nv;
-    Body b;
-    walk_dyn<false>(m, rows, q, u, nullptr, body, b);
+    Chain b;
+    walk_chain<false>(m, rows, q, u, nullptr, true, body, b, NoJoint{});
     const float* x = xtra + body * kXtra;
     const float mass = rows[body * kRow + 7];
-    float po[3], rc[3], r[3], wr[3], fm[3], wb[3], Iwb[3], Iw[3], nm[3], t0[3], vo[3], fe[3], ne[3], B[9];
+    float po[3], rc[3], r[3], wr[3], fm[3], wb[3], Iwb[3], Iw[3], nm[3], t0[3], vo[3], fe[3], ne[3];
     mat3_vec(b.R, x, rc);
     for (int k = 0; k < 3; ++k) { po[k] = b.p[k] - q[k]; r[k] = po[k] + rc[k]; }
     cross3(b.w, rc, wr);
@@ -355,16 +254,7 @@ __global__ __launch_bounds__(kThreads) void aba_kernel(const DevModel* __restric
     cross3(vo, fm, vf);
     cross3(b.w, fm, wf);
     for (int k = 0; k < 3; ++k) { pA[k] = (wn[k] + vf[k]) - ne[k]; pA[3 + k] = wf[k] - fe[k]; }
-    for (int k = 0; k < 3; ++k) {      // B = R I
-      B[3 * k] = b.R[3 * k] * x[3] + b.R[3 * k + 1] * x[4] + b.R[3 * k + 2] * x[5];
-      B[3 * k + 1] = b.R[3 * k] * x[4] + b.R[3 * k + 1] * x[6] + b.R[3 * k + 2] * x[7];
-      B[3 * k + 2] = b.R[3 * k] * x[5] + b.R[3 * k + 1] * x[7] + b.R[3 * k + 2] * x[8];
-    }
-    const float rr = dot3(r, r);
-    int n = 0;
-    for (int i = 0; i < 3; ++i)
-      for (int j = i; j < 3; ++j, ++n)      // (R I R^T)_ij + m (r.r delta_ij - r_i r_j)
-        J[n] = (B[3 * i] * b.R[3 * j] + B[3 * i + 1] * b.R[3 * j + 1] + B[3 * i + 2] * b.R[3 * j + 2]) + mass * ((i == j ? rr : 0.f) - r[i] * r[j]);
+    inertia_about_o(b.R, x + 3, mass, r, J);
     H[1] = -mass * r[2]; H[2] = mass * r[1]; H[3] = mass * r[2]; H[5] = -mass * r[0]; H[6] = -mass * r[1]; H[7] = mass * r[0];      // m [r]x
     M[0] = mass; M[3] = mass; M[5] = mass;
     if (body == 0) {
@@ -453,48 +343,20 @@ __global__ __launch_bounds__(kThreads) void aba_kernel(const DevModel* __restric
 
 // the argument checks both entry points share (after check_world); RSB_OK, or RSB_E_INVALID with a message
 int check_loads(const rsb_world* w, const char* who, const rsb_frame* frames, int n_frames, const float* force, const float* torque, int flags) {
-  if (n_frames < 0 || n_frames > RSB_MAX_FRAMES) { rsb::set_error(std::string(who) + ": n_frames must be 0.." + std::to_string(RSB_MAX_FRAMES)); return RSB_E_INVALID; }
+  if (n_frames < 0 || n_frames > RSB_MAX_FRAMES) return invalid(who, "n_frames must be 0.." + std::to_string(RSB_MAX_FRAMES));
   if (n_frames > 0) {
-    if (!frames) { rsb::set_error(std::string(who) + ": frames is NULL with n_frames > 0"); return RSB_E_INVALID; }
-    if (!force && !torque) { rsb::set_error(std::string(who) + ": force and torque are both NULL with n_frames > 0"); return RSB_E_INVALID; }
+    if (!frames) return invalid(who, "frames is NULL with n_frames > 0");
+    if (!force && !torque) return invalid(who, "force and torque are both NULL with n_frames > 0");
     const int st = check_frames(w, who, frames, n_frames); if (st != RSB_OK) return st;
   }
-  if (flags & ~RSB_DYN_CONTACTS) { rsb::set_error(std::string(who) + ": unknown flag bits"); return RSB_E_INVALID; }
+  if (flags & ~RSB_DYN_CONTACTS) return invalid(who, "unknown flag bits");
   return RSB_OK;
 }
 
-// One query: `in` [N,nv] (udot / tau; may be null), the loads, n_out outputs of width[k] floats per env.  RSB_HOST: everything goes through the
-// world's staging buffer, [in | force | torque | outputs]; copy_out waits for the stream, so the caller may reuse its host buffers on return.
-template <class Launch>
-int run_query(rsb_world* w, const float* in, const rsb_frame* frames, int n_frames, const float* force, const float* torque, int flags, float* const* host,
-              const size_t* width, int n_out, int space, Launch&& launch) {
-  HIP_TRY(hipSetDevice(w->device));
-  const size_t N = (size_t)w->N, nv = (size_t)w->blob.nv, lf = N * (size_t)n_frames * 3;
-  const float *din = in, *df = n_frames ? force : nullptr, *dq = n_frames ? torque : nullptr;
-  float* dev[3] = {nullptr, nullptr, nullptr};
-  for (int k = 0; k < n_out; ++k) dev[k] = host[k];
-  if (space == RSB_HOST) {
-    size_t total = (in ? N * nv : 0) + (df ? lf : 0) + (dq ? lf : 0);
-    for (int k = 0; k < n_out; ++k) if (host[k]) total += N * width[k];
-    int st = staging(w, total); if (st != RSB_OK) return st;
-    hipStream_t s = stream_of(w);
-    float* b = w->d_frames_io;
-    if (in) { HIP_TRY(hipMemcpyAsync(b, in, N * nv * sizeof(float), hipMemcpyHostToDevice, s)); din = b; b += N * nv; }
-    if (df) { HIP_TRY(hipMemcpyAsync(b, force, lf * sizeof(float), hipMemcpyHostToDevice, s)); df = b; b += lf; }
-    if (dq) { HIP_TRY(hipMemcpyAsync(b, torque, lf * sizeof(float), hipMemcpyHostToDevice, s)); dq = b; b += lf; }
-    for (int k = 0; k < n_out; ++k) if (host[k]) { dev[k] = b; b += N * width[k]; }
-  }
+// what the launch hands the kernels: the staged loads (either may be null) and, with RSB_DYN_CONTACTS, the resident contact list
+Loads loads_of(const rsb_world* w, const float* force, const float* torque, int n_frames, int flags) {
   const bool contacts = (flags & RSB_DYN_CONTACTS) != 0;
-  const Loads loads = {df, dq, contacts ? w->d_contacts : nullptr, contacts ? w->d_count : nullptr, n_frames, w->kmax, (float)(1.0 / w->dt)};
-  const FrameList fl = n_frames ? frame_list(frames, n_frames) : FrameList{};
-  const int epb = kThreads / w->blob.nb;
-  const Vec3 g = {(float)w->gravity[0], (float)w->gravity[1], (float)w->gravity[2]};
-  launch(dim3((unsigned)((N + epb - 1) / epb)), stream_of(w), din, fl, loads, g, dev);
-  HIP_TRY(hipGetLastError());
-  if (space == RSB_HOST)
-    for (int k = 0; k < n_out; ++k)
-      if (host[k]) { int st = copy_out(w, host[k], dev[k], N * width[k] * sizeof(float), RSB_HOST); if (st != RSB_OK) return st; }
-  return RSB_OK;
+  return {force, torque, contacts ? w->d_contacts : nullptr, contacts ? w->d_count : nullptr, n_frames, w->kmax, (float)(1.0 / w->dt)};
 }
 
 }  // namespace
@@ -507,30 +369,41 @@ int rsb_inverse_dynamics(rsb_world* w, const float* udot, const rsb_frame* frame
                          float* joint_force, float* joint_torque, int space) {
   const char* who = "rsb_inverse_dynamics";
   int st = check_world(w, who, space); if (st != RSB_OK) return st;
-  if (!tau && !joint_force && !joint_torque) { rsb::set_error(std::string(who) + ": every output is NULL"); return RSB_E_INVALID; }
+  if (!tau && !joint_force && !joint_torque) return invalid(who, "every output is NULL");
   st = check_loads(w, who, frames, n_frames, force, torque, flags); if (st != RSB_OK) return st;
-  float* host[3] = {tau, joint_force, joint_torque};
-  const size_t width[3] = {(size_t)w->blob.nv, (size_t)w->blob.nb * 3, (size_t)w->blob.nb * 3};
-  return run_query(w, udot, frames, n_frames, force, torque, flags, host, width, 3, space,
-                   [&](dim3 grid, hipStream_t s, const float* din, const FrameList& fl, const Loads& loads, const Vec3& g, float* const* dev) {
-                     hipLaunchKernelGGL(rnea_kernel, grid, dim3(kThreads), 0, s, (const DevModel*)w->d_model, (const float*)w->d_gc, (const float*)w->d_gv, din, fl,
-                                        loads, w->N, g, dev[0], dev[1], dev[2]);
-                   });
+  HIP_TRY(hipSetDevice(w->device));
+  const size_t N = (size_t)w->N, nv = (size_t)w->blob.nv, nb3 = (size_t)w->blob.nb * 3, lf = N * (size_t)n_frames * 3;
+  const float *dud, *df, *dq;
+  float *dt, *djf, *djt;
+  Staged io(w, space);      // [udot | force | torque | outputs]; without frames the loads are not read
+  io.in(dud, udot, N * nv); io.in(df, n_frames ? force : nullptr, lf); io.in(dq, n_frames ? torque : nullptr, lf);
+  io.out(dt, tau, N * nv); io.out(djf, joint_force, N * nb3); io.out(djt, joint_torque, N * nb3);
+  st = io.begin(); if (st != RSB_OK) return st;
+  hipLaunchKernelGGL(rnea_kernel, dim3(env_blocks(w)), dim3(kThreads), 0, stream_of(w), (const DevModel*)w->d_model, (const float*)w->d_gc, (const float*)w->d_gv, dud,
+                     n_frames ? frame_list(frames, n_frames) : FrameList{}, loads_of(w, df, dq, n_frames, flags), w->N, gravity_of(w), dt, djf, djt);
+  HIP_TRY(hipGetLastError());
+  return io.end();
 }
 
 int rsb_forward_dynamics(rsb_world* w, const float* tau, const rsb_frame* frames, int n_frames, const float* force, const float* torque, int flags, float* udot,
                          int space) {
   const char* who = "rsb_forward_dynamics";
   int st = check_world(w, who, space); if (st != RSB_OK) return st;
-  if (!udot) { rsb::set_error(std::string(who) + ": the output is NULL"); return RSB_E_INVALID; }
+  if (!udot) return invalid(who, "the output is NULL");
   st = check_loads(w, who, frames, n_frames, force, torque, flags); if (st != RSB_OK) return st;
-  float* host[1] = {udot};
-  const size_t width[1] = {(size_t)w->blob.nv};
-  return run_query(w, tau, frames, n_frames, force, torque, flags, host, width, 1, space,
-                   [&](dim3 grid, hipStream_t s, const float* din, const FrameList& fl, const Loads& loads, const Vec3& g, float* const* dev) {
-                     hipLaunchKernelGGL(aba_kernel, grid, dim3(kThreads), 0, s, (const DevModel*)w->d_model, (const float*)w->d_gc, (const float*)w->d_gv,
-                                        din ? din : (const float*)w->d_tff, fl, loads, w->N, g, dev[0]);
-                   });
+  HIP_TRY(hipSetDevice(w->device));
+  const size_t N = (size_t)w->N, nv = (size_t)w->blob.nv, lf = N * (size_t)n_frames * 3;
+  const float *dt, *df, *dq;
+  float* dud;
+  Staged io(w, space);      // [tau | force | torque | udot]; tau == NULL: the resident feed-forward rows
+  io.in(dt, tau, N * nv); io.in(df, n_frames ? force : nullptr, lf); io.in(dq, n_frames ? torque : nullptr, lf);
+  io.out(dud, udot, N * nv);
+  st = io.begin(); if (st != RSB_OK) return st;
+  hipLaunchKernelGGL(aba_kernel, dim3(env_blocks(w)), dim3(kThreads), 0, stream_of(w), (const DevModel*)w->d_model, (const float*)w->d_gc, (const float*)w->d_gv,
+                     dt ? dt : (const float*)w->d_tff, n_frames ? frame_list(frames, n_frames) : FrameList{}, loads_of(w, df, dq, n_frames, flags), w->N,
+                     gravity_of(w), dud);
+  HIP_TRY(hipGetLastError());
+  return io.end();
 }
 
 }  // extern "C"

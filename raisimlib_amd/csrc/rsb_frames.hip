@@ -4,7 +4,8 @@
 // What ArticulatedSystem::getFramePosition / getFrameOrientation / getFrameVelocity / getFrameAngularVelocity / getDenseFrameJacobian /
 // getDenseFrameRotationalJacobian / setExternalForce / setExternalTorque give for one object on the host [RECALL], for all N envs in one call, from
 // d_gc / d_gv / d_tff on the world's stream.  Nothing here is shared with the step kernel: these are short kernels of their own, called between two
-// control steps.
+// control steps.  What they share with the other batched queries - the chain walk, the argument checks, the staging of the RSB_HOST forms - is in
+// frames_chain.h.
 //
 // A frame is a point fixed in a body (rsb_frame: body, offset in the body frame).  Its support chain is the path root -> body, at most `depth` bodies,
 // listed by DevModel::anc.  Every kernel walks that chain with the running world transform (R, p) and velocity (omega, v) of the current body in
@@ -49,8 +50,7 @@ __global__ __launch_bounds__(kThreads) void frame_kinematics_kernel(const DevMod
   const float* q = gc + (size_t)env * m.nq;
   const float* u = gv + (size_t)env * m.nv;
   Chain c;
-  const auto nothing = [](int, int, const float*, const float*, bool) {};
-  walk_chain(m, rows, q, u, lin_vel || ang_vel, f.body, c, nothing);      // (one instruction stream for the transform, whichever outputs are asked for)
+  walk_chain<false>(m, rows, q, u, nullptr, lin_vel || ang_vel, f.body, c, NoJoint{});      // (one instruction stream for the transform, whichever outputs are asked for)
   float o[3];
   mat3_vec(c.R, f.offset, o);
   if (pos) for (int k = 0; k < 3; ++k) pos[idx * 3 + k] = c.p[k] + o[k];
@@ -81,7 +81,7 @@ __global__ __launch_bounds__(kThreads) void frame_jacobians_kernel(const DevMode
     const float* q = gc + (size_t)env * m.nq;
     float* ch = chains + threadIdx.x * pitch;
     Chain c;
-    walk_chain(m, rows, q, nullptr, false, f.body, c, [ch](int l, int, const float* a, const float* p, bool revolute) {
+    walk_chain<false>(m, rows, q, nullptr, nullptr, false, f.body, c, [ch](int l, int, const float* a, const float* p, bool revolute) {
       float* s = ch + kChainHead + (l - 1) * kChainLevel;
       for (int k = 0; k < 3; ++k) { s[k] = a[k]; s[3 + k] = p[k]; }
       s[6] = revolute ? 1.f : 0.f;
@@ -141,7 +141,8 @@ __global__ __launch_bounds__(kThreads) void external_wrench_kernel(const DevMode
   float fo[3], to[3], pt[3], o[3];
   for (int k = 0; k < 3; ++k) { fo[k] = force ? force[(size_t)env * 3 + k] : 0.f; to[k] = torque ? torque[(size_t)env * 3 + k] : 0.f; }
   Chain c;
-  walk_chain(m, rows, q, nullptr, false, f.body, c, [](int, int, const float*, const float*, bool) {});
+  // (an empty callback of this kernel's own, not NoJoint: profiles/query_common_isa.txt says what the shared one cost when this was written; worth another look with a new compiler)
+  walk_chain<false>(m, rows, q, nullptr, nullptr, false, f.body, c, [](int, int, const float*, const float*, bool) {});
   mat3_vec(c.R, f.offset, o);
   for (int k = 0; k < 3; ++k) pt[k] = c.p[k] + o[k];
   if (!m.fixed_base) {
@@ -150,7 +151,7 @@ __global__ __launch_bounds__(kThreads) void external_wrench_kernel(const DevMode
     cross3(r, fo, rf);
     for (int k = 0; k < 3; ++k) { tau[k] += fo[k]; tau[3 + k] += to[k] + rf[k]; }
   }
-  walk_chain(m, rows, q, nullptr, false, f.body, c, [&](int, int i, const float* a, const float* p, bool revolute) {
+  walk_chain<false>(m, rows, q, nullptr, nullptr, false, f.body, c, [&](int, int i, const float* a, const float* p, bool revolute) {
     float g;
     if (revolute) {
       const float r[3] = {pt[0] - p[0], pt[1] - p[1], pt[2] - p[2]};
@@ -167,7 +168,7 @@ __global__ __launch_bounds__(kThreads) void external_wrench_kernel(const DevMode
 
 }  // namespace
 
-// the staging buffer of the RSB_HOST forms, at least `floats` long (grown between launches: everything enqueued so far is waited for first)
+// the staging buffer of the batched queries' RSB_HOST forms (Staged, frames_chain.h), at least `floats` long (grown between launches: everything enqueued so far is waited for first)
 int staging(rsb_world* w, size_t floats) {
   if (w->frames_io_cap >= floats) return RSB_OK;
   HIP_TRY(hipStreamSynchronize(stream_of(w)));
@@ -192,75 +193,56 @@ int rsb_get_frame_kinematics(rsb_world* w, const rsb_frame* frames, int n_frames
   const char* who = "rsb_get_frame_kinematics";
   int st = check_world(w, who, space); if (st != RSB_OK) return st;
   st = check_frames(w, who, frames, n_frames); if (st != RSB_OK) return st;
-  if (!pos && !rot && !lin_vel && !ang_vel) { rsb::set_error(std::string(who) + ": every output is NULL"); return RSB_E_INVALID; }
+  if (!pos && !rot && !lin_vel && !ang_vel) return invalid(who, "every output is NULL");
   HIP_TRY(hipSetDevice(w->device));
   const size_t pairs = (size_t)w->N * n_frames;
-  float* host[4] = {pos, rot, lin_vel, ang_vel};
-  float* dev[4] = {pos, rot, lin_vel, ang_vel};
-  const size_t width[4] = {3, 9, 3, 3};
-  if (space == RSB_HOST) {
-    st = staging(w, pairs * 18); if (st != RSB_OK) return st;
-    size_t off = 0;
-    for (int k = 0; k < 4; ++k) if (host[k]) { dev[k] = w->d_frames_io + off; off += pairs * width[k]; }
-  }
-  hipLaunchKernelGGL(frame_kinematics_kernel, dim3((unsigned)((pairs + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream_of(w), (const DevModel*)w->d_model,
-                     (const float*)w->d_gc, (const float*)w->d_gv, frame_list(frames, n_frames), n_frames, w->N, dev[0], dev[1], dev[2], dev[3]);
+  float *dp, *dr, *dl, *da;
+  Staged io(w, space);
+  io.out(dp, pos, pairs * 3); io.out(dr, rot, pairs * 9); io.out(dl, lin_vel, pairs * 3); io.out(da, ang_vel, pairs * 3);
+  st = io.begin(); if (st != RSB_OK) return st;
+  hipLaunchKernelGGL(frame_kinematics_kernel, dim3(blocks_for(pairs)), dim3(kThreads), 0, stream_of(w), (const DevModel*)w->d_model, (const float*)w->d_gc,
+                     (const float*)w->d_gv, frame_list(frames, n_frames), n_frames, w->N, dp, dr, dl, da);
   HIP_TRY(hipGetLastError());
-  if (space == RSB_HOST)
-    for (int k = 0; k < 4; ++k)
-      if (host[k]) { st = copy_out(w, host[k], dev[k], pairs * width[k] * sizeof(float), RSB_HOST); if (st != RSB_OK) return st; }
-  return RSB_OK;
+  return io.end();
 }
 
 int rsb_get_frame_jacobians(rsb_world* w, const rsb_frame* frames, int n_frames, float* J_lin, float* J_rot, int space) {
   const char* who = "rsb_get_frame_jacobians";
   int st = check_world(w, who, space); if (st != RSB_OK) return st;
   st = check_frames(w, who, frames, n_frames); if (st != RSB_OK) return st;
-  if (!J_lin && !J_rot) { rsb::set_error(std::string(who) + ": every output is NULL"); return RSB_E_INVALID; }
+  if (!J_lin && !J_rot) return invalid(who, "every output is NULL");
   HIP_TRY(hipSetDevice(w->device));
   const size_t pairs = (size_t)w->N * n_frames, per = pairs * 3 * w->blob.nv;
-  float *dl = J_lin, *dr = J_rot;
-  if (space == RSB_HOST) {
-    st = staging(w, per * 2); if (st != RSB_OK) return st;
-    dl = J_lin ? w->d_frames_io : nullptr;
-    dr = J_rot ? w->d_frames_io + per : nullptr;
-  }
+  float *dl, *dr;
+  Staged io(w, space);
+  io.out(dl, J_lin, per); io.out(dr, J_rot, per);
+  st = io.begin(); if (st != RSB_OK) return st;
   const int pitch = (kChainHead + kChainLevel * std::max(1, w->blob.depth - 1)) | 1;      // odd: the lanes of phase 1 write to different banks
   const int ppb = std::max(1, std::min(64, kJacLdsFloats / pitch));
   const size_t lds = ((size_t)w->blob.nb * kRow + (size_t)ppb * pitch) * sizeof(float);
-  hipLaunchKernelGGL(frame_jacobians_kernel, dim3((unsigned)((pairs + ppb - 1) / ppb)), dim3(kThreads), lds, stream_of(w), (const DevModel*)w->d_model,
-                     (const float*)w->d_gc, frame_list(frames, n_frames), n_frames, w->N, ppb, pitch, dl, dr);
+  hipLaunchKernelGGL(frame_jacobians_kernel, dim3(blocks_for(pairs, ppb)), dim3(kThreads), lds, stream_of(w), (const DevModel*)w->d_model, (const float*)w->d_gc,
+                     frame_list(frames, n_frames), n_frames, w->N, ppb, pitch, dl, dr);
   HIP_TRY(hipGetLastError());
-  if (space == RSB_HOST) {
-    if (J_lin) { st = copy_out(w, J_lin, dl, per * sizeof(float), RSB_HOST); if (st != RSB_OK) return st; }
-    if (J_rot) { st = copy_out(w, J_rot, dr, per * sizeof(float), RSB_HOST); if (st != RSB_OK) return st; }
-  }
-  return RSB_OK;
+  return io.end();
 }
 
 int rsb_add_external_wrench(rsb_world* w, const rsb_frame* frame, const float* force, const float* torque, const uint8_t* mask, int space) {
   const char* who = "rsb_add_external_wrench";
   int st = check_world(w, who, space); if (st != RSB_OK) return st;
   st = check_frames(w, who, frame, frame ? 1 : 0); if (st != RSB_OK) return st;
-  if (!force && !torque) { rsb::set_error(std::string(who) + ": force and torque are both NULL"); return RSB_E_INVALID; }
+  if (!force && !torque) return invalid(who, "force and torque are both NULL");
   HIP_TRY(hipSetDevice(w->device));
   const size_t N = w->N;
-  const float *df = force, *dq = torque;
-  const uint8_t* dm = mask;
-  if (space == RSB_HOST) {      // [force N x 3 | torque N x 3 | mask N bytes] through the staging buffer
-    st = staging(w, 6 * N + (N + 3) / 4); if (st != RSB_OK) return st;
-    hipStream_t s = stream_of(w);
-    float* b = w->d_frames_io;
-    if (force) { HIP_TRY(hipMemcpyAsync(b, force, 3 * N * sizeof(float), hipMemcpyHostToDevice, s)); df = b; }
-    if (torque) { HIP_TRY(hipMemcpyAsync(b + 3 * N, torque, 3 * N * sizeof(float), hipMemcpyHostToDevice, s)); dq = b + 3 * N; }
-    if (mask) { HIP_TRY(hipMemcpyAsync(b + 6 * N, mask, N, hipMemcpyHostToDevice, s)); dm = (const uint8_t*)(b + 6 * N); }
-  }
-  hipLaunchKernelGGL(external_wrench_kernel, dim3((unsigned)((N + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream_of(w), (const DevModel*)w->d_model,
-                     (const float*)w->d_gc, *frame, w->N, df, dq, dm, w->d_tff);
+  const float *df, *dq;
+  const uint8_t* dm;
+  Staged io(w, space);      // no output: end() waits for the stream, the caller may reuse its host buffers
+  io.in(df, force, 3 * N); io.in(dq, torque, 3 * N); io.in(dm, mask, N);
+  st = io.begin(); if (st != RSB_OK) return st;
+  hipLaunchKernelGGL(external_wrench_kernel, dim3(blocks_for(N)), dim3(kThreads), 0, stream_of(w), (const DevModel*)w->d_model, (const float*)w->d_gc, *frame, w->N,
+                     df, dq, dm, w->d_tff);
   HIP_TRY(hipGetLastError());
   w->tff_zero = false;      // the step kernel reads the feed-forward rows from now on
-  if (space == RSB_HOST) HIP_TRY(hipStreamSynchronize(stream_of(w)));      // the caller may reuse its host buffers
-  return RSB_OK;
+  return io.end();
 }
 
 }  // extern "C"

@@ -3,9 +3,10 @@
 //
 // What HeightMap::getHeight / getNormal and World::rayTest give for one world and one point or ray on the host [RECALL], for all N envs in one call,
 // on the world's stream.  Nothing here is shared with the step kernel's instances: these are short kernels of their own, called between two control
-// steps.  There is ONE definition of the surface: every kernel asks rsbk::terrain_eval (step_terrain.h), the function the collider's resolve uses,
-// through a Terrain struct that carries the hm_* fields with the values the step launch gives them.  With per-env maps (rsb_set_heightmaps) an env
-// reads its own map (hm_index).  terrain_eval clamps the coordinates to the map: no query reads outside it, whatever the caller passes.
+// steps.  The chain walk, the argument checks and the staging of the RSB_HOST forms are those of all batched queries (frames_chain.h).  There is ONE
+// definition of the surface: every kernel asks rsbk::terrain_eval (step_terrain.h), the function the collider's resolve uses, through a Terrain struct
+// that carries the hm_* fields with the values the step launch gives them.  With per-env maps (rsb_set_heightmaps) an env reads its own map
+// (hm_index).  terrain_eval clamps the coordinates to the map: no query reads outside it, whatever the caller passes.
 //
 //   terrain_height_kernel  one lane per (env, point): height and unit normal of the triangle under the point.
 //   height_scan_kernel     the hot path: out[env, frame, k] = p_z - h(p_xy + M pattern[k]), p the frame's world position.  Two phases, as
@@ -69,7 +70,7 @@ __global__ __launch_bounds__(kThreads) void height_scan_kernel(const DevModel* _
     const rsb_frame f = frames.f[fr];
     const float* q = gc + (size_t)env * m.nq;
     Chain c;
-    walk_chain(m, rows, q, nullptr, false, f.body, c, [](int, int, const float*, const float*, bool) {});
+    walk_chain<false>(m, rows, q, nullptr, nullptr, false, f.body, c, NoJoint{});
     float o[3];
     mat3_vec(c.R, f.offset, o);
     float* r = recs + threadIdx.x * kPairRec;
@@ -184,10 +185,6 @@ Terrain terrain_of(const rsb_world* w) {       // as do_integrate fills StepArgs
   return t;
 }
 
-int invalid(const char* who, const std::string& what) { rsb::set_error(std::string(who) + ": " + what); return RSB_E_INVALID; }
-
-unsigned blocks_for(size_t lanes) { return (unsigned)((lanes + kThreads - 1) / kThreads); }
-
 }  // namespace
 }  // namespace rsbw
 using namespace rsbw;
@@ -202,22 +199,14 @@ int rsb_get_terrain_height(rsb_world* w, const float* xy, int n_points, float* h
   if (!height && !normal) return invalid(who, "every output is NULL");
   HIP_TRY(hipSetDevice(w->device));
   const size_t total = (size_t)w->N * n_points;
-  const float* dxy = xy;
-  float *dh = height, *dn = normal;
-  hipStream_t s = stream_of(w);
-  if (space == RSB_HOST) {      // [xy 2 | height 1 | normal 3] floats per point through the staging buffer
-    st = staging(w, total * 6); if (st != RSB_OK) return st;
-    float* b = w->d_frames_io;
-    HIP_TRY(hipMemcpyAsync(b, xy, total * 2 * sizeof(float), hipMemcpyHostToDevice, s));
-    dxy = b; dh = height ? b + total * 2 : nullptr; dn = normal ? b + total * 3 : nullptr;
-  }
-  hipLaunchKernelGGL(terrain_height_kernel, dim3(blocks_for(total)), dim3(kThreads), 0, s, terrain_of(w), dxy, n_points, (long long)total, dh, dn);
+  const float* dxy;
+  float *dh, *dn;
+  Staged io(w, space);
+  io.in(dxy, xy, total * 2); io.out(dh, height, total); io.out(dn, normal, total * 3);
+  st = io.begin(); if (st != RSB_OK) return st;
+  hipLaunchKernelGGL(terrain_height_kernel, dim3(blocks_for(total)), dim3(kThreads), 0, stream_of(w), terrain_of(w), dxy, n_points, (long long)total, dh, dn);
   HIP_TRY(hipGetLastError());
-  if (space == RSB_HOST) {
-    if (height) { st = copy_out(w, height, dh, total * sizeof(float), RSB_HOST); if (st != RSB_OK) return st; }
-    if (normal) { st = copy_out(w, normal, dn, total * 3 * sizeof(float), RSB_HOST); if (st != RSB_OK) return st; }
-  }
-  return RSB_OK;
+  return io.end();
 }
 
 int rsb_height_scan(rsb_world* w, const rsb_frame* frames, int n_frames, const float* pattern, int n_points, int mode, float* out, long long row_stride,
@@ -233,19 +222,16 @@ int rsb_height_scan(rsb_world* w, const rsb_frame* frames, int n_frames, const f
   if (row_stride < width) return invalid(who, "row_stride " + std::to_string(row_stride) + " is smaller than n_frames * n_points = " + std::to_string(width));
   HIP_TRY(hipSetDevice(w->device));
   const size_t N = w->N, pairs = N * n_frames;
-  const float* dp = pattern;
-  float* dout = out;
-  long long dstride = row_stride;
+  const float* dp;
+  float* dout;
+  Staged io(w, space);      // RSB_HOST: the scan is staged dense; its rows go to the caller's stride on the way back, below, not through end()
+  io.in(dp, pattern, (size_t)n_points * 2); io.out(dout, out, N * width);
+  st = io.begin(); if (st != RSB_OK) return st;
+  const long long dstride = space == RSB_HOST ? width : row_stride;
   hipStream_t s = stream_of(w);
-  if (space == RSB_HOST) {      // [pattern P x 2 | out N x F x P, dense]: the rows go to the caller's stride on the way back
-    st = staging(w, (size_t)n_points * 2 + N * width); if (st != RSB_OK) return st;
-    float* b = w->d_frames_io;
-    HIP_TRY(hipMemcpyAsync(b, pattern, (size_t)n_points * 2 * sizeof(float), hipMemcpyHostToDevice, s));
-    dp = b; dout = b + (size_t)n_points * 2; dstride = width;
-  }
   const int ppb = std::max(1, std::min(64, (4 * kThreads + n_points - 1) / n_points));      // phase 2 sweeps about four blocks' worth of outputs
   const size_t lds = ((size_t)w->blob.nb * kRow + (size_t)n_points * 2 + (size_t)ppb * kPairRec) * sizeof(float);
-  hipLaunchKernelGGL(height_scan_kernel, dim3((unsigned)((pairs + ppb - 1) / ppb)), dim3(kThreads), lds, s, (const DevModel*)w->d_model, (const float*)w->d_gc,
+  hipLaunchKernelGGL(height_scan_kernel, dim3(blocks_for(pairs, ppb)), dim3(kThreads), lds, s, (const DevModel*)w->d_model, (const float*)w->d_gc,
                      frame_list(frames, n_frames), n_frames, w->N, terrain_of(w), dp, n_points, mode, ppb, dout, dstride);
   HIP_TRY(hipGetLastError());
   if (space == RSB_HOST) {
@@ -265,20 +251,14 @@ int rsb_ray_test(rsb_world* w, const float* origins, const float* directions, in
   if (!(max_dist > 0.f) || !std::isfinite(max_dist)) return invalid(who, "max_dist must be positive and finite");
   HIP_TRY(hipSetDevice(w->device));
   const size_t total = (size_t)w->N * n_rays;
-  const float *dor = origins, *ddi = directions;
-  float* dd = dist;
-  hipStream_t s = stream_of(w);
-  if (space == RSB_HOST) {      // [origins 3 | directions 3 | dist 1] floats per ray through the staging buffer
-    st = staging(w, total * 7); if (st != RSB_OK) return st;
-    float* b = w->d_frames_io;
-    HIP_TRY(hipMemcpyAsync(b, origins, total * 3 * sizeof(float), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(b + total * 3, directions, total * 3 * sizeof(float), hipMemcpyHostToDevice, s));
-    dor = b; ddi = b + total * 3; dd = b + total * 6;
-  }
-  hipLaunchKernelGGL(ray_test_kernel, dim3(blocks_for(total)), dim3(kThreads), 0, s, terrain_of(w), dor, ddi, n_rays, (long long)total, max_dist, dd);
+  const float *dor, *ddi;
+  float* dd;
+  Staged io(w, space);
+  io.in(dor, origins, total * 3); io.in(ddi, directions, total * 3); io.out(dd, dist, total);
+  st = io.begin(); if (st != RSB_OK) return st;
+  hipLaunchKernelGGL(ray_test_kernel, dim3(blocks_for(total)), dim3(kThreads), 0, stream_of(w), terrain_of(w), dor, ddi, n_rays, (long long)total, max_dist, dd);
   HIP_TRY(hipGetLastError());
-  if (space == RSB_HOST) { st = copy_out(w, dist, dd, total * sizeof(float), RSB_HOST); if (st != RSB_OK) return st; }
-  return RSB_OK;
+  return io.end();
 }
 
 }  // extern "C"

@@ -227,7 +227,7 @@ int rk4_integrate(rsb_world* w, int nsub, const StepRequest& req);   // rsb_rk4.
 int obs_stats_init(rsb_world* w);                                 // rsb_obstats.hip: the observation statistics at their initial state (rsb_env_configure, once)
 void obs_stats_free(rsb_world* w);                                // rsb_obstats.hip (rsb_destroy)
 void frames_free(rsb_world* w);                                   // rsb_frames.hip (rsb_destroy)
-int staging(rsb_world* w, size_t floats);                         // rsb_frames.hip: d_frames_io, the staging buffer of the RSB_HOST forms of the frame and terrain queries, at least `floats` long
+int staging(rsb_world* w, size_t floats);                         // rsb_frames.hip: d_frames_io, the staging buffer of every batched query's RSB_HOST form (Staged, frames_chain.h), at least `floats` long
 // rsb_pipeline.hip
 hipStream_t stream_of(rsb_world* w);                              // the world's stream for any use other than a pipelined launch (joins first)
 int pipe_join(rsb_world* w);
