@@ -251,6 +251,28 @@ class BatchedWorld {
     std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
     RSB_CHECK(rsb_get_frame_jacobians(world_, frames.data(), (int)frames.size(), Jlin, Jrot, RSB_HOST));
   }
+  /// ArticulatedSystem::getFrameAcceleration for ALL envs in one call, on the device, at the resident state (staged view rows are uploaded first):
+  /// linAcc [N,F,3] the classical acceleration of the frame's point (d/dt of linVel above) = Jlin udot + dJlin/dt gv, angAcc [N,F,3] the angular
+  /// acceleration of its body; either may be null.  udot [N,dof()]: the component-wise derivative of gv, as inverseDynamics takes it (null: zeros -
+  /// the bias terms).  World frame; local: in the axes of the frame's body (R^T x); proper: linAcc minus the world's gravity - the specific force.
+  void getFrameAccelerations(const std::vector<rsb_frame>& frames, const float* udot, bool local, bool proper, float* linAcc, float* angAcc) {
+    std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
+    RSB_CHECK(rsb_get_frame_accelerations(world_, frames.data(), (int)frames.size(), udot, (local ? RSB_ACC_LOCAL : 0) | (proper ? RSB_ACC_PROPER : 0), linAcc, angAcc,
+                                          RSB_HOST));
+  }
+  /// getTimeDerivativeOfSparseJacobian / getTimeDerivativeOfSparseRotationalJacobian for all envs, dense: dJlin, dJrot [N,F,3,dof()] (either may be
+  /// null), d/dt of getFrameJacobians along the resident gv: linAcc = Jlin udot + dJlin gv for every udot; a fixed base keeps its six (zero) columns
+  void getFrameJacobianRates(const std::vector<rsb_frame>& frames, float* dJlin, float* dJrot) {
+    std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
+    RSB_CHECK(rsb_get_frame_jacobian_rates(world_, frames.data(), (int)frames.size(), dJlin, dJrot, RSB_HOST));
+  }
+  /// The IMU rows of an observation for all envs: out[e * rowStride + 6 f + 0..2] = R^T (linAcc - g) (accelerometer), + 3..5 = R^T omega (gyro), udot
+  /// as in getFrameAccelerations (after a step: forwardDynamics of the applied force with contacts).  rowStride in floats, 0 = 6 F; a larger one
+  /// leaves the other columns of a row alone.
+  void getImuReadings(const std::vector<rsb_frame>& frames, const float* udot, float* out, long long rowStride = 0) {
+    std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
+    RSB_CHECK(rsb_imu_observe(world_, frames.data(), (int)frames.size(), udot, out, rowStride, RSB_HOST));
+  }
   /// setExternalForce / setExternalTorque for all envs: adds J^T force[e] + Jrot^T torque[e] (world frame, [N,3] each, either may be null)
   /// to the feed-forward row of every env with mask[e] != 0 (null: all).  Same lifetime as the per-env calls: until setGeneralizedForce / clearExternalForces.
   void addExternalWrench(const rsb_frame& frame, const float* force, const float* torque, const uint8_t* mask = nullptr) {

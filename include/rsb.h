@@ -31,6 +31,10 @@
  *                                       <- ArticulatedSystem::getFramePosition/getFrameOrientation/getFrameVelocity/
  *                                          getFrameAngularVelocity/getDenseFrameJacobian/getDenseFrameRotationalJacobian/
  *                                          setExternalForce/setExternalTorque, for all envs in one call
+ *   rsb_get_frame_accelerations / rsb_get_frame_jacobian_rates / rsb_imu_observe
+ *                                       <- ArticulatedSystem::getFrameAcceleration / getTimeDerivativeOfSparseJacobian /
+ *                                          getTimeDerivativeOfSparseRotationalJacobian, and (new) the accelerometer + gyro rows of an
+ *                                          observation, for all envs in one call
  *   rsb_inverse_dynamics / rsb_forward_dynamics
  *                                       <- ArticulatedSystem::setComputeInverseDynamics / getForceAtJointInWorldFrame /
  *                                          getTorqueAtJointInWorldFrame, and the plain equations of motion, for all envs in one call
@@ -289,6 +293,48 @@ int rsb_get_frame_jacobians(rsb_world* w, const rsb_frame* frames, int n_frames,
  * It stays in RSB_F_TAU_FF until rsb_set_generalized_force replaces it (upstream clears external forces after every integrate()). */
 int rsb_add_external_wrench(rsb_world* w, const rsb_frame* frame, const float* force, const float* torque,
                             const uint8_t* mask, int space);
+
+/* Frame accelerations, Jacobian rates and IMU readings of ALL envs in one call, from the resident state [RECALL upstream's per-object
+ * ArticulatedSystem::getFrameAcceleration / getTimeDerivativeOfSparseJacobian / getTimeDerivativeOfSparseRotationalJacobian]: HIP kernels on the
+ * world's stream, like the frame queries above (a pipelined world is joined first); the RSB_DEVICE forms do not synchronise, the RSB_HOST forms stage
+ * through the same device buffer.  frames as in rsb_get_frame_kinematics (a HOST array).  The base quaternion is normalised first.  None of the three
+ * changes a bit of the world: state, warm state, contact records, what rsb_integrate1 left and the feed-forward rows stay as they are.  An error
+ * touches no output.  Fixed-base model: the base neither moves nor accelerates - no bit of the base rows of gv / udot matters.
+ *
+ * udot [N,nv] in `space` is the component-wise time derivative of gv, the convention of rsb_inverse_dynamics: udot[0:3] is the classical
+ * acceleration of the base origin (d/dt of its world velocity), udot[3:6] the world angular acceleration of the base.  NULL = zeros.
+ *
+ * rsb_get_frame_accelerations: with (R, omega_i, alpha_i) of the frame's body i, ac_i the classical acceleration of its origin and o = R offset,
+ *   lin_acc [N,F,3] = J_lin udot + Jdot_lin gv = ac_i + alpha_i x o + omega_i x (omega_i x o), d/dt of lin_vel of rsb_get_frame_kinematics;
+ *   ang_acc [N,F,3] = J_rot udot + Jdot_rot gv = alpha_i;                         either may be NULL, not both.
+ * With udot NULL these are the bias terms Jdot_lin gv, Jdot_rot gv.  World frame; flags: RSB_ACC_LOCAL - both outputs multiplied by R^T (the axes of
+ * the frame's body, R = rot of rsb_get_frame_kinematics); RSB_ACC_PROPER - lin_acc minus the world's gravity vector (rsb_set_gravity): the specific
+ * force at the point, what an accelerometer there reads.  Unknown flag bits: RSB_E_INVALID.
+ *
+ * rsb_get_frame_jacobian_rates: Jdot_lin, Jdot_rot [N,F,3,nv] (either may be NULL), d/dt of the matrices of rsb_get_frame_jacobians along the
+ * resident gv: lin_acc = J_lin udot + Jdot_lin gv and ang_acc = J_rot udot + Jdot_rot gv for every udot.  Columns in this ABI's order; fixed-base
+ * model: the six base columns zero.
+ *
+ * rsb_imu_observe: the fused IMU rows of an observation.  For env e and frame f
+ *   out[e * row_stride + 6 f + 0..2] = R^T (lin_acc - g)   (accelerometer: RSB_ACC_LOCAL | RSB_ACC_PROPER of the call above, the same bits)
+ *   out[e * row_stride + 6 f + 3..5] = R^T omega           (gyro)
+ * row_stride, in floats: 0 = 6 F (a dense [N,F,6] output); larger values write into columns [0, 6 F) of rows of that pitch - pass a pointer into a
+ * wider observation tensor - and touch no other float, as rsb_height_scan does; smaller non-zero values are RSB_E_INVALID.
+ * RSB_E_INVALID, with a message: a null world; a bad `space`; every output NULL; n_frames outside 1..RSB_MAX_FRAMES, a frame whose body is out of
+ * range or whose offset is not finite; unknown flag bits; a bad row_stride. */
+#define RSB_ACC_LOCAL  1   /* outputs in the axes of the frame's body: R^T x, R = rot of rsb_get_frame_kinematics */
+#define RSB_ACC_PROPER 2   /* lin_acc minus the world's gravity vector (rsb_set_gravity): the specific force at the point */
+int rsb_get_frame_accelerations(rsb_world* w, const rsb_frame* frames, int n_frames,
+                                const float* udot,    /* [N,nv] in `space`; NULL = zeros: the outputs are then the bias terms Jdot_lin gv, Jdot_rot gv */
+                                int flags,
+                                float* lin_acc,       /* [N,F,3] */
+                                float* ang_acc,       /* [N,F,3]  either may be NULL, not both */
+                                int space);
+int rsb_get_frame_jacobian_rates(rsb_world* w, const rsb_frame* frames, int n_frames,
+                                 float* Jdot_lin, float* Jdot_rot,   /* [N,F,3,nv], either may be NULL, not both */
+                                 int space);
+int rsb_imu_observe(rsb_world* w, const rsb_frame* frames, int n_frames, const float* udot,
+                    float* out, long long row_stride, int space);
 
 /* Whole-body quantities of ALL envs in one call, from the resident state [RECALL upstream's per-object ArticulatedSystem::getCOM / getLinearMomentum /
  * getAngularMomentum / getKineticEnergy / getPotentialEnergy / getEnergy]: HIP kernels on the world's stream, like the frame queries above (ordered with

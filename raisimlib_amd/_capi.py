@@ -52,6 +52,7 @@ RSB_MAX_FRAMES = 64
 RSB_MAX_SCAN_POINTS = 1024
 RSB_DYN_CONTACTS = 1
 RSB_SCAN_WORLD, RSB_SCAN_YAW = 0, 1
+RSB_ACC_LOCAL, RSB_ACC_PROPER = 1, 2
 
 
 class TerrainProperties(C.Structure):
@@ -202,6 +203,9 @@ PROTOTYPES = {
     "rsb_get_frame_kinematics": (_I, [_VP, C.POINTER(Frame), _I, _FP, _FP, _FP, _FP, _I]),
     "rsb_get_frame_jacobians": (_I, [_VP, C.POINTER(Frame), _I, _FP, _FP, _I]),
     "rsb_add_external_wrench": (_I, [_VP, C.POINTER(Frame), _FP, _FP, _FP, _I]),
+    "rsb_get_frame_accelerations": (_I, [_VP, C.POINTER(Frame), _I, _FP, _I, _FP, _FP, _I]),
+    "rsb_get_frame_jacobian_rates": (_I, [_VP, C.POINTER(Frame), _I, _FP, _FP, _I]),
+    "rsb_imu_observe": (_I, [_VP, C.POINTER(Frame), _I, _FP, _FP, C.c_longlong, _I]),
     "rsb_get_centroidal": (_I, [_VP, _FP, _FP, _FP, _FP, _FP, _FP, _I]),
     "rsb_get_centroidal_momentum_matrix": (_I, [_VP, _FP, _I]),
     "rsb_inverse_dynamics": (_I, [_VP, _FP, C.POINTER(Frame), _I, _FP, _FP, _I, _FP, _FP, _FP, _I]),

@@ -38,7 +38,8 @@ HOST_SOURCES = {   # source -> headers it depends on
     "rsb_terrain_query.hip": _WORLD_DEPS + ["frames_chain.h", "step_terrain.h", "step_math.h"],   # batched terrain heights, height scans and ray tests
     "rsb_centroidal.hip": _WORLD_DEPS + ["frames_chain.h"],  # batched centre of mass, momentum, energy and the centroidal momentum matrix
     "rsb_dynamics.hip": _WORLD_DEPS + ["frames_chain.h"],    # batched inverse dynamics with joint reaction wrenches, contact-free forward dynamics
-    "rsb_spec.hip": _WORLD_DEPS,       # specialised code objects of the step kernel: key, cache directory, compile, load, launch
+    "rsb_frame_accel.hip": _WORLD_DEPS + ["frames_chain.h"], # batched frame accelerations, frame Jacobian rates and IMU readings
+    "rsb_spec.hip": _WORLD_DEPS,      # specialised code objects of the step kernel: key, cache directory, compile, load, launch
 }
 # the fused step kernel: the template's skeleton (step_kernel.h), its device helpers (step_math / step_terrain / step_slip .h) and its body, one
 # fragment per phase (step_phase_*.inc, included inside the kernel: same token stream as the one 2 500-line function of rounds 1-4)

@@ -525,6 +525,64 @@ class BatchedWorld:
         check(self.L.rsb_get_frame_jacobians(self.handle, arr, n, *ptrs, space), "rsb_get_frame_jacobians")
         return out
 
+    def _udot_input(self, what, udot, device):
+        """udot [N, nv] or None -> (C argument, what must stay alive until the call returns); a torch CUDA tensor with torch outputs (RSB_DEVICE),
+        anything else is taken as a float32 host array (RSB_HOST), as _dynamics_inputs does"""
+        args, keep = self._dynamics_inputs(("udot", what), udot, None, device)
+        return args[0], keep
+
+    def frame_accelerations(self, frames, udot=None, local=False, proper=False, lin=True, ang=False, out=None):
+        """ArticulatedSystem::getFrameAcceleration of every env at once -> {"lin": [N, F, 3], "ang": [N, F, 3]}, the outputs asked for only: the
+        classical acceleration of the frame's point (d/dt of lin_vel of frame_kinematics) = J_lin udot + Jdot_lin gv, and the angular acceleration
+        of its body = J_rot udot + Jdot_rot gv, at the resident state.  udot [N, nv]: the component-wise derivative of gv, the convention of
+        inverse_dynamics (None: zeros - the bias terms Jdot gv).  World frame; local=True: in the axes of the frame's body (R^T x); proper=True:
+        lin minus the world's gravity vector, the specific force at the point.  out: see _frame_outputs; torch outputs take a torch udot."""
+        arr, n = self._frames(frames)
+        shapes = {"lin": (self.N, n, 3), "ang": (self.N, n, 3)}
+        space, ptrs, out = self._frame_outputs(("lin", "ang"), dict(lin=lin, ang=ang), shapes, out, "frame_accelerations")
+        ud, keep = self._udot_input("frame_accelerations", udot, space == RSB_DEVICE)
+        flags = (_capi.RSB_ACC_LOCAL if local else 0) | (_capi.RSB_ACC_PROPER if proper else 0)
+        check(self.L.rsb_get_frame_accelerations(self.handle, arr, n, ud, flags, *ptrs, space), "rsb_get_frame_accelerations")
+        return out
+
+    def frame_jacobian_rates(self, frames, lin=True, rot=False, out=None):
+        """getTimeDerivativeOfSparseJacobian / getTimeDerivativeOfSparseRotationalJacobian of every env at once, dense -> {"lin": [N, F, 3, nv],
+        "rot": [N, F, 3, nv]}: d/dt of frame_jacobians along the resident gv, so that frame_accelerations = J @ udot + Jdot @ gv for every udot
+        (a fixed-base model keeps its six, zero, base columns)."""
+        arr, n = self._frames(frames)
+        shapes = {"lin": (self.N, n, 3, self.nv), "rot": (self.N, n, 3, self.nv)}
+        space, ptrs, out = self._frame_outputs(("lin", "rot"), dict(lin=lin, rot=rot), shapes, out, "frame_jacobian_rates")
+        check(self.L.rsb_get_frame_jacobian_rates(self.handle, arr, n, *ptrs, space), "rsb_get_frame_jacobian_rates")
+        return out
+
+    def imu_observe(self, frames, udot=None, out=None, row_stride=0):
+        """The IMU rows of an observation: [N, F, 6], out[e, f, 0:3] = R^T (lin_acc - g) (accelerometer: the specific force at the frame's point in
+        the axes of its body), out[e, f, 3:6] = R^T omega (gyro); udot as in frame_accelerations (after a control step: forward_dynamics of the
+        applied force with contacts=True).  row_stride (floats, 0 = 6 F): with a larger value `out` is the first IMU column of a wider
+        [N, row_stride] buffer - a torch view such as obs[:, k:] (only its data pointer is used) or a numpy array of N * row_stride floats - whose
+        other columns are left alone.  A torch `out` takes a torch udot (RSB_DEVICE, no synchronisation)."""
+        arr, F = self._frames(frames)
+        width = 6 * F
+        stride = int(row_stride) or width
+        if stride == width:
+            space, ptrs, res = self._frame_outputs(("out",), dict(out=True), {"out": (self.N, F, 6)}, None if out is None else {"out": out}, "imu_observe")
+            ud, keep = self._udot_input("imu_observe", udot, space == RSB_DEVICE)
+            check(self.L.rsb_imu_observe(self.handle, arr, F, ud, ptrs[0], 0, space), "rsb_imu_observe")
+            return res["out"]
+        if out is None:
+            raise ValueError("imu_observe: a row_stride needs `out`")
+        if self._is_torch(out):
+            if not (out.is_cuda and str(out.dtype) == "torch.float32" and out.device.index == self.device):
+                raise ValueError(f"imu_observe: out must be a float32 CUDA tensor on cuda:{self.device}")
+            space, optr = RSB_DEVICE, C.c_void_p(out.data_ptr())
+        else:
+            if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and (stride < width or out.size >= (self.N - 1) * stride + width)):
+                raise ValueError("imu_observe: out must be a C-contiguous float32 array that holds N rows of row_stride floats")
+            space, optr = RSB_HOST, _hp(out)
+        ud, keep = self._udot_input("imu_observe", udot, space == RSB_DEVICE)
+        check(self.L.rsb_imu_observe(self.handle, arr, F, ud, optr, stride, space), "rsb_imu_observe")
+        return out
+
     def add_external_wrench(self, frame, force=None, torque=None, mask=None):
         """setExternalForce / setExternalTorque of every env at once: tau_ff[e] += J_lin(e)^T force[e] + J_rot(e)^T torque[e] at the current state
         for the envs with mask[e] != 0 (None: all).  force / torque [N, 3] world frame, mask [N] uint8: numpy arrays, or torch CUDA tensors (no
