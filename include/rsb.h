@@ -167,7 +167,10 @@ int rsb_set_integration_scheme(rsb_world* w, int scheme);
 int rsb_set_max_contacts(rsb_world* w, int kmax);   /* 1..RSB_MAX_CONTACTS */
 
 int rsb_set_ground(rsb_world* w, double height);
-/* heights: host pointer, row-major [y_samples][x_samples] (x fastest), shared by all envs */
+/* heights: host pointer, row-major [y_samples][x_samples] (x fastest), shared by all envs.
+ * Beyond the footprint the terrain is the surface the queries below name: the height at the coordinates clamped to the footprint, level across
+ * the border.  The collider follows it: a primitive whose centre is outside the footprint gets depth = r - (z - h(clamped x, clamped y)) and
+ * normal (0, 0, 1); a centre inside it (the border included) touches the closest feature of the triangulated surface, which ends at the border. */
 int rsb_set_heightmap(rsb_world* w, int x_samples, int y_samples, double x_size, double y_size,
                       double center_x, double center_y, const float* heights);
 /* terrain curricula: n_maps height maps of one geometry, heights [n_maps][y_samples][x_samples] (host), and the map

@@ -535,8 +535,8 @@ static void closest_on_triangle(const double* a, const double* b, const double* 
  * Plane: depth = r - (c_z - z0), normal = z.  Height map: the CLOSEST FEATURE (face, edge or vertex) of the triangulated
  * surface over the cells the sphere's xy bounding square overlaps (at most ORC_HM_CELLS x ORC_HM_CELLS of them, scanned
  * row by row, the lower-right triangle of a cell first; the first of equally close features wins): normal = from the
- * closest point to the centre, depth = r - distance.  A centre at or below the surface, or beyond the map's border, falls
- * back to the plane of the triangle under it (see the end of the function).
+ * closest point to the centre, depth = r - distance.  A centre at or below the surface falls back to the plane of the
+ * triangle under it, a centre beyond the map's border to the height at the clamped coordinates with normal z (see the end of the function).
  * Upstream counterpart: the sphere x HeightMap collider of RaiSim's vendored ODE - absent from /root/reference. */
 #define ORC_HM_CELLS 3
 /* depth2 / n2 (may be NULL): with orc_params::hm_contacts >= 2 a sphere in a valley also reports the closest feature of a SECOND flank -
@@ -638,11 +638,15 @@ static int terrain_contact_ex(const orc_params* p, const double* c, double r, do
       }
     }
   } else {
-    /* the centre is at or below the surface (a zero-radius box corner, a sphere pushed in by more than its radius) or beyond
-     * the map's border (the terrain continues flat from its outermost samples): the triangle UNDER the centre decides -
-     * depth = r - distance to its plane, normal = its face normal */
+    /* the centre is at or below the surface (a zero-radius box corner, a sphere pushed in by more than its radius): the triangle
+     * UNDER the centre decides - depth = r - distance to its plane, normal = its face normal.
+     * Beyond the map's border the surface is the one the terrain queries name (rsb_set_heightmap): the height at the coordinates
+     * clamped to the footprint, level across the border - depth = r - (c_z - h), normal = z.  (The tilted plane of the outermost
+     * triangle, continued outwards, rose above every sample beside a steep border cell and reported spheres floating over the whole
+     * map, which the device's cull by the highest sample drops.) */
     double h;
     orc_terrain(p, c[0], c[1], &h, n);
+    if (!inside) { n[0] = 0.0; n[1] = 0.0; n[2] = 1.0; }
     *depth = r - (c[2] - h) * n[2];
   }
   return *depth > 0.0;

@@ -113,7 +113,8 @@ __device__ __forceinline__ void terrain_eval(const Args& a, const float* heights
   n[0] = -gxs * inv; n[1] = -gys * inv; n[2] = inv;
 }
 // closest point bp (relative to the centre (x, y, z)) on a triangle with face normal bn -> penetration depth and unit contact
-// normal; a centre at / below the surface or beyond the map's border falls back to the plane of the triangle under it
+// normal; a centre at / below the surface falls back to the plane of the triangle under it, a centre beyond the map's border to the surface of
+// the terrain queries: depth = r - (z - h(clamped x, clamped y)), normal = z
 // Round 5: "the centre is outside the terrain" is decided by the HEIGHT FIELD (z above the surface at (x, y)), read from the slot's own patch of
 // corner heights (LDS: the patch always holds the cell under the clamped centre) - not by the plane of the triangle that holds the closest point,
 // which past a convex edge sharper than the sphere is close answered with the wrong feature (oracle: terrain_contact_ex, above_test; VERDICT r04 #4a).
@@ -137,10 +138,13 @@ __device__ __forceinline__ bool hm_resolve(const Args& a, const float* patch, in
   const float inv = 1.0f / sqrtf(gxs * gxs + gys * gys + 1.0f);
   const bool feature = inside & (z > h) & (dist > 1e-9f);   // (returned: the contact is the closest feature's, not the fallback's)
   const float id = 1.0f / fmaxf(dist, 1e-30f);
-  n[0] = feature ? -bp[0] * id : -gxs * inv;
-  n[1] = feature ? -bp[1] * id : -gys * inv;
-  n[2] = feature ? -bp[2] * id : inv;
-  depth = feature ? r - dist : r - (z - h) * inv;
+  // beyond the border the surface is the one of the queries: the height at the clamped coordinates, normal z (never above the corners scanned,
+  // so the culls by hm_max and by the patch's maximum stay exact)
+  const float pz = inside ? inv : 1.0f;
+  n[0] = feature ? -bp[0] * id : (inside ? -gxs * inv : 0.f);
+  n[1] = feature ? -bp[1] * id : (inside ? -gys * inv : 0.f);
+  n[2] = feature ? -bp[2] * id : pz;
+  depth = feature ? r - dist : r - (z - h) * pz;
   return feature;
 }
 
@@ -180,8 +184,8 @@ __device__ __forceinline__ void hm_resolve_above(const Args& a, const float* hei
     RSB_UNROLL for (int i = 0; i < 3; ++i) n[i] = -bp[i] * id;
     depth = r - dist;
   } else {
-    RSB_UNROLL for (int i = 0; i < 3; ++i) n[i] = nh[i];
-    depth = r - (z - h) * nh[2];
+    RSB_UNROLL for (int i = 0; i < 3; ++i) n[i] = inside ? nh[i] : (i == 2 ? 1.0f : 0.f);     // beyond the border: the clamped height, normal z
+    depth = r - (z - h) * n[2];
   }
 }
 
