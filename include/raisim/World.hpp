@@ -334,6 +334,38 @@ class BatchedWorld {
     std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
     RSB_CHECK(rsb_ray_test(world_, origins, directions, nRays, maxDist, dist, RSB_HOST));
   }
+  /// World::rayTest against the terrain AND the robot's collision bodies for all envs (rsb_ray_cast in rsb.h): origins, directions [N,R,3] world
+  /// frame -> dist [N,R] in metres, -1 for a miss (missMax: maxDist), hit [N,R]: RSB_RAY_HIT_NONE, RSB_RAY_HIT_TERRAIN or the first collision
+  /// primitive of the shape that was hit; either output may be null, not both.  The shapes are the model's spheres, capsules, cylinders and boxes; a
+  /// mesh collider is invisible to rays.  bodies = false: what rayTest gives, bit for bit.  Host buffers.
+  void rayCast(const float* origins, const float* directions, int nRays, float maxDist, float* dist, int32_t* hit = nullptr, bool bodies = true,
+               bool missMax = false) {
+    std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
+    RSB_CHECK(rsb_ray_cast(world_, origins, directions, nRays, maxDist, (bodies ? RSB_RAY_BODIES : 0) | (missMax ? RSB_RAY_MISS_MAX : 0), dist, hit, RSB_HOST));
+  }
+  /// A depth camera or lidar mounted on a body, for all envs (rsb_ray_scan in rsb.h): out[e * rowStride + f * P + k] = range from frame f's world
+  /// point along R_body dirs[k], dirs [P,3] in the axes of the frame's body (x forward, y left, z up; any length), P <= RSB_MAX_RAY_POINTS.  A frame
+  /// has no orientation of its own: a tilted sensor rotates its pattern once.  flags: RSB_RAY_BODIES (rays stop at the robot too), RSB_RAY_OWN_BODY
+  /// (also at the frame's own body), RSB_RAY_PLANAR (range times the cosine to the body's x axis: a depth image), RSB_RAY_MISS_MAX (a miss is
+  /// maxDist, not -1).  rowStride as in heightScan; hit [N,F,P] dense, may be null (so may out, not both).  Host buffers.
+  void rayScan(const std::vector<rsb_frame>& frames, const float* dirs, int nPoints, float maxDist, float* out, long long rowStride = 0,
+               int flags = RSB_RAY_BODIES, int32_t* hit = nullptr) {
+    std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
+    RSB_CHECK(rsb_ray_scan(world_, frames.data(), (int)frames.size(), dirs, nPoints, flags, maxDist, out, rowStride, hit, RSB_HOST));
+  }
+  /// The pattern of a pinhole camera looking along +x for rayScan: unit directions [height * width, 3] through the pixel centres, row-major (row 0
+  /// the top row, column 0 the left one), square pixels, hfov the horizontal field of view in radians.
+  static std::vector<float> depthCameraRays(int width, int height, double hfov) {
+    std::vector<float> d((size_t)width * height * 3);
+    const double focal = 0.5 * width / std::tan(0.5 * hfov);
+    for (int r = 0; r < height; ++r)
+      for (int c = 0; c < width; ++c) {
+        const double y = -(c + 0.5 - 0.5 * width), z = -(r + 0.5 - 0.5 * height), in = 1.0 / std::sqrt(focal * focal + y * y + z * z);
+        float* o = d.data() + ((size_t)r * width + c) * 3;
+        o[0] = (float)(focal * in); o[1] = (float)(y * in); o[2] = (float)(z * in);
+      }
+    return d;
+  }
 
   // batched, caller-owned host buffers (row-major [N, dim] float32, the raisimGymTorch matrix layout)
   void setState(const float* gc, const float* gv) {

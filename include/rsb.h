@@ -41,6 +41,8 @@
  *   rsb_get_terrain_height / rsb_height_scan / rsb_ray_test
  *                                       <- HeightMap::getHeight / getNormal, World::rayTest (against the terrain), for all envs
  *                                          in one call                                (HeightMap.hpp, World.hpp, absent)
+ *   rsb_ray_cast / rsb_ray_scan         <- World::rayTest against the terrain AND the robot's collision bodies, and (new) its fused
+ *                                          sensor form: a depth camera or lidar mounted on a body, for all envs in one call
  *   rsb_gather_obs                      <- (new) the (q, u, contact-force) observation block that
  *                                          VectorizedEnvironment::observe() is built from
  *   rsb_env_observe_normalized / rsb_env_get_obs_stats / rsb_env_set_obs_stats
@@ -429,6 +431,47 @@ int rsb_height_scan(rsb_world* w, const rsb_frame* frames, int n_frames, const f
  * Ground plane: the infinite plane.  A ray with a zero or non-finite direction or a non-finite origin gives -1.  max_dist must be positive and
  * finite.  There is no normal output: feed the hit's xy to rsb_get_terrain_height. */
 int rsb_ray_test(rsb_world* w, const float* origins, const float* directions, int n_rays, float max_dist, float* dist, int space);
+
+/* Rays that also stop at the robot, and ray patterns mounted on a body (a depth camera, a lidar): World::rayTest upstream hits every object of the
+ * world [RECALL]; rsb_ray_test above sees the terrain only.  Both calls read the resident gc alone (base quaternion normalised first, a fixed base's
+ * base rows as the world keeps them), change no bit of the world, join a pipelined world as the other queries do, and touch no output when they
+ * return an error.
+ *
+ * The robot's shapes, built once per world from the model's collision primitives in index order:
+ *   col_capsule[s] == -1                     an oriented box from its eight corners s .. s + 7
+ *   col_capsule[s] = e + 1, col_rim[s] == 0  a capsule between the centres of primitives s and e, radius col_radius[s]
+ *   col_capsule[s] = e + 1, col_rim[s] > 0   a cylinder with flat caps between the centres of s and e, radius col_rim[s]
+ *   any other primitive with col_radius > 0  a sphere (the extra spheres of a sampled capsule lie inside it and change nothing)
+ * Zero-radius points - a mesh's hull vertices, the lattice of a sampled box, a lone rim - have no surface: a MESH collider is invisible to rays.
+ * A body hit is the first s >= 0 at which the ray is on or inside a shape; an origin inside a shape gives 0, as an origin under the terrain does.
+ *
+ * flags: RSB_RAY_BODIES    rays stop at the shapes above as well as at the terrain; without it the calls see what rsb_ray_test sees
+ *        RSB_RAY_MISS_MAX  a miss reports max_dist, not -1
+ *        RSB_RAY_OWN_BODY, RSB_RAY_PLANAR: rsb_ray_scan only, below.  Unknown bits are RSB_E_INVALID.
+ * hit (int32, optional): RSB_RAY_HIT_NONE, RSB_RAY_HIT_TERRAIN, or the index of the FIRST collision primitive of the shape that was hit
+ * (rsb_model_blob::col_body / col_name of it name the link).
+ *
+ * rsb_ray_cast, the world-space form: origins, directions [N,R,3] in `space` -> dist [N,R], hit [N,R]; either output may be NULL, not both.  With
+ * flags == 0 dist is rsb_ray_test's, bit for bit.  With RSB_RAY_BODIES dist is the smaller of the terrain hit and the first body entry (a tie is the
+ * terrain's); where the terrain wins dist carries rsb_ray_test's bits: the terrain march always runs with the call's max_dist and is never
+ * shortened by a body hit - one definition of the terrain answer, for the price of an optimisation.  RSB_RAY_OWN_BODY and RSB_RAY_PLANAR are
+ * RSB_E_INVALID here: a world-space ray has no frame. */
+int rsb_ray_cast(rsb_world* w, const float* origins, const float* directions, int n_rays, float max_dist, int flags,
+                 float* dist, int32_t* hit, int space);
+/* rsb_ray_scan, the sensor form: for every env e, frame f (a HOST array, as in rsb_get_frame_kinematics) and pattern direction k
+ *   out[e * row_stride + f * P + k] = range from the frame's world point along R_body(f) dirs[k],
+ * dirs [P,3] in `space`, expressed in the axes of the frame's body, of any length (normalised as rsb_ray_test normalises); a zero or non-finite
+ * direction gives a miss.  P = n_points <= RSB_MAX_RAY_POINTS.  Our axis convention for the pattern helpers: x forward, y left, z up ([RECALL]-
+ * unknown: upstream's sensor axes cannot be read from the stub).  An rsb_frame has no orientation of its own: a sensor tilted against its body
+ * rotates its pattern on the host, once.
+ *   RSB_RAY_OWN_BODY  the shapes of the frame's own body are tested too (default: a sensor sees through its mount)
+ *   RSB_RAY_PLANAR    out = range * (unit direction . the body's x axis): the depth image of a pinhole camera looking along x, not the range along
+ *                     the ray; with RSB_RAY_MISS_MAX a miss is max_dist times the same cosine (1 for a direction that cannot be cast)
+ * row_stride as in rsb_height_scan: 0 = F * P (dense [N,F,P]); a larger value writes columns [0, F * P) of rows of that pitch and touches no other
+ * column; a smaller non-zero value is RSB_E_INVALID.  hit is dense [N,F,P].  Either of out, hit may be NULL, not both.  A ray's result does not
+ * depend on which other frames or directions the call lists. */
+int rsb_ray_scan(rsb_world* w, const rsb_frame* frames, int n_frames, const float* dirs, int n_points, int flags, float max_dist,
+                 float* out, long long row_stride, int32_t* hit, int space);
 
 /* obs block [N, nq+nv+3*n_force_slots] = (q, u, contact force on chosen collision primitives).
  * collision_indices: host array of n_force_slots collision-primitive indices (e.g. the feet);

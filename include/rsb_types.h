@@ -123,6 +123,15 @@ typedef enum rsb_scan_mode {
   RSB_SCAN_YAW = 1                /* pattern rotated about z by the frame's heading */
 } rsb_scan_mode;
 
+/* Ray casts and sensor-mounted ray scans that also see the robot (rsb_ray_cast, rsb_ray_scan; rsb.h): bits of their `flags` argument, codes of `hit` */
+#define RSB_MAX_RAY_POINTS 4096   /* pattern directions of one rsb_ray_scan call (staged in LDS, 48 KB) */
+#define RSB_RAY_BODIES   1  /* rays also stop at the robot's collision shapes (rsb.h) */
+#define RSB_RAY_OWN_BODY 2  /* rsb_ray_scan only: also test the shapes of the frame's own body (default: a sensor sees through its mount) */
+#define RSB_RAY_PLANAR   4  /* rsb_ray_scan only: report range * (unit direction . frame x axis), a depth image, not the range along the ray */
+#define RSB_RAY_MISS_MAX 8  /* a miss reports max_dist (PLANAR: times the same cosine), not -1 */
+#define RSB_RAY_HIT_NONE    (-1)
+#define RSB_RAY_HIT_TERRAIN (-2)   /* hit >= 0: index of the FIRST collision primitive of the shape that was hit (col_body / col_name of it name the link) */
+
 /* Dynamics queries (rsb_inverse_dynamics, rsb_forward_dynamics; rsb.h): bits of their `flags` argument */
 #define RSB_DYN_CONTACTS 1        /* bit 0: the resident contact list acts, each record as the world force impulse / dt at its position on its body */
 

@@ -8,3 +8,4 @@ from ._capi import (RSB_DEVICE, RSB_FORCE_AND_TORQUE, RSB_HOST, RSB_MAX_CONTACTS
                     RSB_PD_PLUS_FEEDFORWARD_TORQUE, RsbError)
 from .world import CONTACT_DTYPE, BatchedWorld, Model, rsc_path  # noqa: F401
 from .vecenv import VecEnv  # noqa: F401
+from .rays import depth_camera_rays, lidar_rays  # noqa: F401

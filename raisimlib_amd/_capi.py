@@ -52,6 +52,9 @@ RSB_MAX_FRAMES = 64
 RSB_MAX_SCAN_POINTS = 1024
 RSB_DYN_CONTACTS = 1
 RSB_SCAN_WORLD, RSB_SCAN_YAW = 0, 1
+RSB_MAX_RAY_POINTS = 4096
+RSB_RAY_BODIES, RSB_RAY_OWN_BODY, RSB_RAY_PLANAR, RSB_RAY_MISS_MAX = 1, 2, 4, 8
+RSB_RAY_HIT_NONE, RSB_RAY_HIT_TERRAIN = -1, -2
 RSB_ACC_LOCAL, RSB_ACC_PROPER = 1, 2
 
 
@@ -213,6 +216,8 @@ PROTOTYPES = {
     "rsb_get_terrain_height": (_I, [_VP, _FP, _I, _FP, _FP, _I]),
     "rsb_height_scan": (_I, [_VP, C.POINTER(Frame), _I, _FP, _I, _I, _FP, C.c_longlong, _I]),
     "rsb_ray_test": (_I, [_VP, _FP, _FP, _I, C.c_float, _FP, _I]),
+    "rsb_ray_cast": (_I, [_VP, _FP, _FP, _I, C.c_float, _I, _FP, _VP, _I]),
+    "rsb_ray_scan": (_I, [_VP, C.POINTER(Frame), _I, _FP, _I, _I, C.c_float, _FP, C.c_longlong, _VP, _I]),
     "rsb_obs_dim": (_I, [_VP, _I]),
     "rsb_gather_obs": (_I, [_VP, _FP, _FP, _I, _I]),
     "rsb_reset_terminated": (_I, [_VP, _FP, _I, _FP, _FP, _I, _FP, _I]),

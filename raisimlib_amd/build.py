@@ -36,6 +36,7 @@ HOST_SOURCES = {   # source -> headers it depends on
     "rsb_obstats.hip": _WORLD_DEPS,    # running observation statistics of the env task: moments, merge, normalise
     "rsb_frames.hip": _WORLD_DEPS + ["frames_chain.h"],     # batched frame kinematics, frame Jacobians and external wrenches from the resident state
     "rsb_terrain_query.hip": _WORLD_DEPS + ["frames_chain.h", "step_terrain.h", "step_math.h"],   # batched terrain heights, height scans and ray tests
+    "rsb_ray_scan.hip": _WORLD_DEPS + ["frames_chain.h", "step_terrain.h", "step_math.h", "terrain_ray.h"],   # ray casts and sensor-mounted ray scans that also hit the robot
     "rsb_centroidal.hip": _WORLD_DEPS + ["frames_chain.h"],  # batched centre of mass, momentum, energy and the centroidal momentum matrix
     "rsb_dynamics.hip": _WORLD_DEPS + ["frames_chain.h"],    # batched inverse dynamics with joint reaction wrenches, contact-free forward dynamics
     "rsb_frame_accel.hip": _WORLD_DEPS + ["frames_chain.h"], # batched frame accelerations, frame Jacobian rates and IMU readings

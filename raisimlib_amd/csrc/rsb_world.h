@@ -145,6 +145,8 @@ struct rsb_world {
   int obs_part_batches = 0;
   // batched frame and terrain queries (rsb_frames.hip, rsb_terrain_query.hip): staging of the RSB_HOST forms' inputs / outputs, grown on demand
   float* d_frames_io = nullptr; size_t frames_io_cap = 0;
+  // ray casts against the robot (rsb_ray_scan.hip): the model's collision shapes as rays see them, body frame, built from the blob on first use
+  float* d_ray_shapes = nullptr; int n_ray_shapes = -1;      // (-1: not built yet)
   std::vector<hipEvent_t> ring0, ring1;   // event pairs around the most recent step-kernel launches (rsb_enable_timing(w, n))
   size_t ring_next = 0, ring_count = 0;
   int timing_stride = 1;       // events bracket every timing_stride-th launch only (an event pair costs ~7 us of stream time)
@@ -227,7 +229,8 @@ int rk4_integrate(rsb_world* w, int nsub, const StepRequest& req);   // rsb_rk4.
 int obs_stats_init(rsb_world* w);                                 // rsb_obstats.hip: the observation statistics at their initial state (rsb_env_configure, once)
 void obs_stats_free(rsb_world* w);                                // rsb_obstats.hip (rsb_destroy)
 void frames_free(rsb_world* w);                                   // rsb_frames.hip (rsb_destroy)
-int staging(rsb_world* w, size_t floats);                         // rsb_frames.hip: d_frames_io, the staging buffer of every batched query's RSB_HOST form (Staged, frames_chain.h), at least `floats` long
+void ray_shapes_free(rsb_world* w);                               // rsb_ray_scan.hip (rsb_destroy)
+int staging(rsb_world* w, size_t floats);                       // rsb_frames.hip: d_frames_io, the staging buffer of every batched query's RSB_HOST form (Staged, frames_chain.h), at least `floats` long
 // rsb_pipeline.hip
 hipStream_t stream_of(rsb_world* w);                              // the world's stream for any use other than a pipelined launch (joins first)
 int pipe_join(rsb_world* w);

@@ -827,6 +827,7 @@ int rsb_destroy(rsb_world* w) {
   if (w->d_env_gc0_rows) { (void)hipFree(w->d_env_gc0_rows); (void)hipFree(w->d_env_gv0_rows); }
   obs_stats_free(w);
   frames_free(w);
+  ray_shapes_free(w);
   if (w->own_stream && w->stream) (void)hipStreamDestroy(w->stream);
   delete w;
   return RSB_OK;

@@ -774,6 +774,92 @@ class BatchedWorld:
         check(self.L.rsb_ray_test(self.handle, ins[0], ins[1], R, float(max_dist), outs[0], space), "rsb_ray_test")
         return res["dist"]
 
+    # -- rays that also hit the robot, and ray patterns mounted on a body (rsb_ray_scan.hip) --------------------------------
+    def _ray_hit_buffer(self, what, dev, given, shape, wanted):
+        """the optional int32 `hit` output of ray_cast / ray_scan -> (pointer or None, array / tensor or None)"""
+        if given is None and not wanted:
+            return None, None
+        cnt = int(np.prod(shape))
+        if dev:
+            if given is None:
+                raise ValueError(f"{what}: with torch inputs pass hit as an int32 torch tensor (out={{'hit': ...}})")
+            if not (self._is_torch(given) and given.is_cuda and given.is_contiguous() and str(given.dtype) == "torch.int32" and given.numel() == cnt
+                    and given.device.index == self.device):
+                raise ValueError(f"{what}: hit must be a contiguous int32 CUDA tensor of {cnt} elements on cuda:{self.device}")
+            return C.c_void_p(given.data_ptr()), given
+        if given is None:
+            given = np.empty(shape, np.int32)
+        if not (isinstance(given, np.ndarray) and given.dtype == np.int32 and given.flags.c_contiguous and given.size == cnt):
+            raise ValueError(f"{what}: hit must be a C-contiguous int32 array of {cnt} elements")
+        return _hp(given), given
+
+    @staticmethod
+    def _ray_flags(bodies, own_body=False, planar=False, miss_max=False):
+        return ((_capi.RSB_RAY_BODIES if bodies else 0) | (_capi.RSB_RAY_OWN_BODY if own_body else 0) | (_capi.RSB_RAY_PLANAR if planar else 0)
+                | (_capi.RSB_RAY_MISS_MAX if miss_max else 0))
+
+    def ray_cast(self, origins, directions, max_dist, bodies=True, hit=False, miss_max=False, out=None):
+        """World::rayTest against the terrain AND the robot for every env at once: origins, directions [N, R, 3] world frame (directions of any
+        length) -> dist [N, R], metres to the first hit within max_dist, -1 for a miss (max_dist with miss_max); with hit=True (dist, hit), hit
+        [N, R] int32: RSB_RAY_HIT_NONE, RSB_RAY_HIT_TERRAIN or the first collision primitive of the shape that was hit (model.blob.col_body /
+        col_name of it name the link).  bodies: rays stop at the robot's collision shapes (spheres, capsules, cylinders, boxes - see rsb_ray_cast in
+        rsb.h; a mesh collider is invisible); bodies=False gives ray_test's answer bit for bit.  out: the dist array / tensor, or {"dist": ..,
+        "hit": ..} (either alone is enough); torch CUDA inputs need torch outputs and do not synchronise."""
+        R = int(np.prod(origins.shape)) // (3 * self.N)
+        outs = dict(out) if isinstance(out, dict) else ({} if out is None else {"dist": out})
+        if set(outs) - {"dist", "hit"}:
+            raise ValueError(f"ray_cast: unknown outputs {sorted(set(outs) - {'dist', 'hit'})}")
+        dev = self._is_torch(origins)
+        want_dist = "dist" in outs or not dev or "hit" not in outs
+        space, ins, optrs, res, _keep = self._terrain_io("ray_cast", {"origins": (origins, (self.N, R, 3)), "directions": (directions, (self.N, R, 3))},
+                                                         {"dist": (self.N, R)} if want_dist else {}, {k: v for k, v in outs.items() if k == "dist"})
+        hptr, harr = self._ray_hit_buffer("ray_cast", dev, outs.get("hit"), (self.N, R), hit)
+        check(self.L.rsb_ray_cast(self.handle, ins[0], ins[1], R, float(max_dist), self._ray_flags(bodies, miss_max=miss_max),
+                                  optrs[0] if want_dist else None, hptr, space), "rsb_ray_cast")
+        if harr is not None and want_dist:
+            return res["dist"], harr
+        return res["dist"] if want_dist else harr
+
+    def ray_scan(self, frames, dirs, max_dist, bodies=True, own_body=False, planar=False, miss_max=False, hit=False, out=None, row_stride=0):
+        """A depth camera or lidar mounted on a body, for every env at once: [N, F, P], out[e, f, k] = range from frame f's world point along
+        R_body dirs[k], dirs [P, 3] in the axes of the frame's body (x forward, y left, z up; any length) - depth_camera_rays / lidar_rays build
+        such patterns; a sensor tilted against its body rotates its pattern once, on the host.  frames as in frame_kinematics.  -1 for a miss
+        (miss_max: max_dist).  bodies: rays stop at the robot's collision shapes too; own_body: also at those of the frame's own body (default: a
+        sensor sees through its mount); planar: range times the cosine to the body's x axis, the depth image of a pinhole camera.  hit=True: (out,
+        hit), hit [N, F, P] int32 as in ray_cast.  out: the range array / tensor, or {"out": .., "hit": ..}.  row_stride as in height_scan."""
+        arr, F = self._frames(frames)
+        P = int(np.prod(dirs.shape)) // 3
+        width = F * P
+        stride = int(row_stride) or width
+        outs = dict(out) if isinstance(out, dict) else ({} if out is None else {"out": out})
+        if set(outs) - {"out", "hit"}:
+            raise ValueError(f"ray_scan: unknown outputs {sorted(set(outs) - {'out', 'hit'})}")
+        dev = self._is_torch(dirs)
+        flags = self._ray_flags(bodies, own_body, planar, miss_max)
+        hptr, harr = self._ray_hit_buffer("ray_scan", dev, outs.get("hit"), (self.N, F, P), hit)
+        rng = outs.get("out")
+        want_out = rng is not None or not dev or harr is None
+        if stride == width:
+            space, ins, optrs, res, _keep = self._terrain_io("ray_scan", {"dirs": (dirs, (P, 3))}, {"out": (self.N, F, P)} if want_out else {}, {"out": rng})
+            optr, rng = (optrs[0], res["out"]) if want_out else (None, None)
+            stride = 0
+        else:
+            if rng is None or self._is_torch(rng) != dev:
+                raise ValueError("ray_scan: a row_stride needs `out`, of the pattern's kind (torch tensor or numpy array)")
+            space, ins, _, _, _keep = self._terrain_io("ray_scan", {"dirs": (dirs, (P, 3))}, {}, {})
+            if dev:
+                if not (rng.is_cuda and str(rng.dtype) == "torch.float32" and rng.device.index == self.device):
+                    raise ValueError(f"ray_scan: out must be a float32 CUDA tensor on cuda:{self.device}")
+                optr = C.c_void_p(rng.data_ptr())
+            else:
+                if not (isinstance(rng, np.ndarray) and rng.dtype == np.float32 and rng.flags.c_contiguous and rng.size >= (self.N - 1) * stride + width):
+                    raise ValueError("ray_scan: out must be a C-contiguous float32 array that holds N rows of row_stride floats")
+                optr = _hp(rng)
+        check(self.L.rsb_ray_scan(self.handle, arr, F, ins[0], P, flags, float(max_dist), optr, stride, hptr, space), "rsb_ray_scan")
+        if harr is not None and rng is not None:
+            return rng, harr
+        return rng if rng is not None else harr
+
     # -- observation block for the vectorised env / RCCL gather --------------------------------------
     def obs_dim(self, n_force_slots):
         return self.L.rsb_obs_dim(self.handle, int(n_force_slots))
