@@ -337,6 +337,9 @@ __global__ void __launch_bounds__(64) RSB_X_WPE_ATTR rsb_step_kernel(const StepA
   [[maybe_unused]] float sc_q = 0.f, sc_qd = 0.f;      // body lane: the own joint's position and velocity
   [[maybe_unused]] float sc_qv[7], sc_uv[6];           // every lane: the base's position, quaternion | velocity
 #endif
+#if RSB_LEAN_SEAM
+#include "step_phase_seam_setup.inc"
+#endif
 #if RSB_RESIDENT
   for (int cs = 0; cs < ncs; ++cs) {
 #endif
@@ -344,6 +347,11 @@ __global__ void __launch_bounds__(64) RSB_X_WPE_ATTR rsb_step_kernel(const StepA
   // The registers are filled from LDS once per control step, never per launch: this point follows the prologue (a new launch, a set_state, a set_pd_target) and,
   // in the resident classes, the epilogue's boundary code (a reset env's state, the next control step's targets) - behind the barrier either of them ends with.
   // Within the sub-steps of one control step nothing but the update pass writes Q and U.
+  // (Lean seam, step_spec.h: behind a control step that reset no env of the wave the registers ARE the rows - what the update pass stored it also kept - and the
+  //  fill is skipped.)
+#if RSB_LEAN_SEAM
+  if (seam_refill)
+#endif
   {
 #if RSB_SEAM_BASE
     float t0[8], t1[8];
@@ -383,7 +391,18 @@ __global__ void __launch_bounds__(64) RSB_X_WPE_ATTR rsb_step_kernel(const StepA
   }  // substeps
 
   if (PROF && a.prof && lane == 0) { long long* P = a.prof + 16 + 16 * (long long)blk; P[8] = t_setup; P[9] = t_newt; P[10] = t_epi; P[11] = t_rule; P[12] = t_exch; P[13] = t_end; P[14] = t_start - t_entry; P[15] = t_mag; P[0] = clock64() - t_start; P[1] = t_gs; P[2] = p_iters; P[3] = p_ncw; P[4] = p_search; P[5] = p_newton; P[6] = p_solves; P[7] = t_srch; }
+#if RSB_LEAN_SEAM
+  if (ls_ok && cs + 1 < ncs) {
+#include "step_phase_seam_lean.inc"
+  } else {
+    seam_refill = true;
+    asm volatile("; rsb generic seam begin");
+#endif
 #include "step_phase_epilogue.inc"
+#if RSB_LEAN_SEAM
+    asm volatile("; rsb generic seam end");
+  }
+#endif
 #if RSB_RESIDENT
   }  // control steps
 #endif

@@ -108,6 +108,28 @@ constexpr float spec_f32(int bits) { return __builtin_bit_cast(float, bits); }
 #define RSB_SEAM_LOADS 0
 #endif
 
+// Lean seam between two control steps of ONE resident launch, in the specialised open-loop resident code objects of the quadruped classes (kernel class 64 at 16
+// lanes per env and eight contact slots, a coordinate row of 17..32 and a q | u row of 33..48 floats: three row entries per lane, the targets' two): a control
+// step that is not the launch's last leaves through step_phase_seam_lean.inc instead of the generic epilogue and boundary code (step_phase_epilogue.inc).  What is
+// constant for the launch - the lane's row pointers into the observation block, the done flags, the target bank and the reset rows, the strides, the lane's
+// obs_idx entry, do_reset, allowed - is formed once in front of the control-step loop (step_phase_seam_setup.inc); the seam itself has no trip loop and no scalar
+// load: one batch of LDS reads with one wait, the stores, the foot forces handed from the contact lanes to the slot lanes by row broadcasts, the next targets
+// requested at its top and stored at its end, the Delassus rows zeroed by unrolled stores.  Where the seam carry runs, its registers are refilled from LDS only
+// behind a control step that reset an env of the wave.  The last control step, res_full launches, launches that ask for tau2_out / a reward / the task's
+// observation or have no obs block or more force slots than lanes per env, the closed-loop classes (| 128, | 256), the humanoid, the ahead-of-time classes and
+// every non-resident class run the generic code.
+// -DRSB_X_NO_LEAN_SEAM compiles the code as it was: same results bit for bit (tests/test_gpu_lean_seam.py).
+// (-DRSB_X_SEAM_BOUND is the deletion experiment that bounded this work - the lean path without the finite check, the obs and done stores, the zeroing and the target
+//  reload; its results are wrong by design: profiles/lean_seam_bound.txt.)
+// (The path reads nothing from the carried registers and does not ask for the seam carry or the quad forms: the switches of those - -DRSB_X_NO_DOWN_QUADS ... -
+//  compare two forms of a tree pass, the same seam on both sides.)
+#if defined(RSB_SPECIALIZED) && defined(RSB_I_CL) && (RSB_I_CL) == 64 && (RSB_I_LPE) == 16 && (RSB_I_KMAX) == 8 && RSB_SPEC_NQ > 16 && RSB_SPEC_NQ <= 32 && \
+    RSB_SPEC_NQ + RSB_SPEC_NV > 32 && RSB_SPEC_NQ + RSB_SPEC_NV <= 48 && !defined(RSB_X_NO_LEAN_SEAM)
+#define RSB_LEAN_SEAM 1
+#else
+#define RSB_LEAN_SEAM 0
+#endif
+
 namespace rsbk {
 #define RSB_SPEC_COUNT_ONE(NAME, expr) +1
 constexpr int kSpecFields = 0 RSB_SPEC_FIELDS(RSB_SPEC_COUNT_ONE);
