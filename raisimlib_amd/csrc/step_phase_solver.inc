@@ -542,6 +542,37 @@
           if constexpr (LPE > 16) {   // body lanes beyond the env's first row need the sum too (level-1 bodies start from the base's delta-velocity)
             RSB_UNROLL for (int i = 0; i < 6; ++i) wlam[i] = __shfl(wlam[i], (lane & ~(LPE - 1)) | (lane & 15));
           }
+#if RSB_FLAT_CLASS
+          asm volatile("; rsb scatter begin");     // (tests/test_flat_contact_host.py counts between the comment lines)
+#endif
+#if RSB_FLAT_SCATTER
+          if (isc) {
+            // flat form (step_spec.h): ONE region, the contact lanes'; inside it the atomics are issued straight, in their level order, behind every read.  A level
+            // the body has no ancestor at adds onto the sink of the lane's own column - another address, so the lanes of an instruction that do add onto WB are
+            // served in the order they always were.  (The lanes WITHOUT a contact stay masked off: an LDS float atomic costs per active lane, and forty-eight more
+            // of them per instruction measured - 4 % on the benchmark, one sink for all of them or one per lane: DESIGN.md section 9.)
+            const int bi = __float_as_int(CON[s * kConSlot + 7]);
+            int anc[4] = {0, -1, -1, -1};
+#if RSB_SPEC_DEPTH == 4
+            { const int4 r4 = *reinterpret_cast<const int4*>(ANC + bi * 4); anc[1] = r4.y; anc[2] = r4.z; anc[3] = r4.w; }
+#else
+            RSB_UNROLL for (int lv = 1; lv < RSB_SPEC_DEPTH; ++lv) anc[lv] = ANC[bi * RSB_SPEC_DEPTH + lv];
+#endif
+            float* sink = WC + 3 * s * cw + kFlatSink;
+            // (every read in front of the first atomic: the compiler moves no load across one)
+            float wl[4] = {0.f, 0.f, 0.f, 0.f};
+            RSB_UNROLL for (int lv = 1; lv < RSB_SPEC_DEPTH; ++lv) {
+              float w0, w1, w2;
+              if (lv < 3) { w0 = z0[5 + lv]; w1 = z1[5 + lv]; w2 = z2[5 + lv]; }
+              else { w0 = W0[5 + lv]; w1 = W0[cw + 5 + lv]; w2 = W0[2 * cw + 5 + lv]; }
+              wl[lv] = w0 * l0 + w1 * l1 + w2 * l2;
+            }
+            RSB_UNROLL for (int lv = 1; lv < RSB_SPEC_DEPTH; ++lv) {
+              float* dst = (anc[lv] >= 0) ? &WB[anc[lv] + 5] : sink;
+              atomicAdd(dst, wl[lv]);
+            }
+          }
+#else
           if (isc) {
             const int bi = __float_as_int(CON[s * kConSlot + 7]);
             // (all ancestors first: read inside the loop, every one waits for its own LDS round trip - the compiler cannot move a load across the atomic before it)
@@ -559,6 +590,10 @@
               }
             }
           }
+#endif
+#if RSB_FLAT_CLASS
+          asm volatile("; rsb scatter end");
+#endif
         }
       }
       __syncthreads();

@@ -130,6 +130,52 @@ constexpr float spec_f32(int bits) { return __builtin_bit_cast(float, bits); }
 #define RSB_LEAN_SEAM 0
 #endif
 
+// Flat contact form, in the specialised code objects of trees of at most four levels at 16 lanes per env, four factor levels and eight contact slots or fewer (the
+// quadruped's lock-step, pipelined, resident and closed-loop classes): the contact columns (step_phase_columns.inc) and the impulse scatter that ends the solve
+// (step_phase_solver.inc, W^T lam) without an exec-mask region per tree level.  Every `if (l < lev)` of those loops was a region with LDS traffic inside, which
+// keeps its skip branch and its own lgkmcnt(0); in the usual wave every contact is a foot at the deepest level, every region is entered and no branch skips anything.
+//   RSB_FLAT_COLUMNS  the level loop runs to the compile-time depth; a level the contact's body does not have reads the FACT row and the WB entry of body 1 (a child
+//                     of the base in every tree: always valid, always written by this sub-step's up pass), its arithmetic runs, and its RESULTS are discarded by
+//                     selects (never by a product with a zero: x - f * 0 turns -0 into +0, and a stale row may be non-finite); its column entry goes to the sink, a
+//                     padding entry of the lane's own column that nobody reads (kFlatSink below).  No load sits in a region, so all of them can be in flight
+//                     together.  Joint-limit rows and the J u record of a self-collision entry sit behind ONE wave-uniform branch.
+//   RSB_FLAT_SCATTER  ONE region, the contact lanes'; inside it every read comes first and the three atomic adds are issued straight, in their level order; a level
+//                     the body has no ancestor at (-1) adds onto the sink of the lane's own column instead (not a zero onto a live entry: lane order within an
+//                     instruction, and so every sum, is what it was).  The lanes without a contact stay masked off: an LDS float atomic costs per ACTIVE lane, and
+//                     the form that let them add onto a sink too - one for all of them, or one per lane - measured 4-5 % BELOW the regions.
+// The form needs a padding entry in the column: cw = round4(6 + depth - 1) > 6 + depth - 1 (depth 2 and 4 of the depths up to 4).
+// -DRSB_X_NO_FLAT_CONTACT compiles the code as it was, -DRSB_X_NO_FLAT_COLUMNS / -DRSB_X_NO_FLAT_SCATTER one part of it: same results bit for bit
+// (tests/test_gpu_flat_contact.py).  RSB_FLAT_CLASS marks the code objects the form applies to, switch or not: they carry the comment lines `; rsb columns begin/end`
+// and `; rsb scatter begin/end` in their assembly (tests/test_flat_contact_host.py counts between them).
+#if defined(RSB_SPECIALIZED) && defined(RSB_I_LPE) && (RSB_I_LPE) == 16 && (RSB_I_KMAX) <= 8 && (RSB_I_ML) <= 4 && RSB_SPEC_DEPTH >= 2 && RSB_SPEC_DEPTH <= 4 && \
+    RSB_SPEC_DEPTH <= (RSB_I_ML) && ((6 + RSB_SPEC_DEPTH - 1 + 3) & ~3) > 6 + RSB_SPEC_DEPTH - 1
+#define RSB_FLAT_CLASS 1
+#else
+#define RSB_FLAT_CLASS 0
+#endif
+#if RSB_FLAT_CLASS && !defined(RSB_X_NO_FLAT_CONTACT)
+#define RSB_FLAT_CONTACT 1
+#else
+#define RSB_FLAT_CONTACT 0
+#endif
+#if RSB_FLAT_CONTACT && !defined(RSB_X_NO_FLAT_COLUMNS)
+#define RSB_FLAT_COLUMNS 1
+#else
+#define RSB_FLAT_COLUMNS 0
+#endif
+#if RSB_FLAT_CONTACT && !defined(RSB_X_NO_FLAT_SCATTER)
+#define RSB_FLAT_SCATTER 1
+#else
+#define RSB_FLAT_SCATTER 0
+#endif
+#if RSB_FLAT_CLASS
+namespace rsbk {
+// the sink: the last entry of a contact column [z 0..5 | levels 1..depth-1 | padding].  Nothing reads the padding: the scatter and the Delassus rows stop at 5 + depth - 1.
+constexpr int kFlatCw = (6 + RSB_SPEC_DEPTH - 1 + 3) & ~3, kFlatSink = kFlatCw - 1;
+static_assert(kFlatSink >= 6 + RSB_SPEC_DEPTH - 1 && kFlatSink < kFlatCw, "flat contact form: the sink must be a padding entry of the column");
+}  // namespace rsbk
+#endif
+
 namespace rsbk {
 #define RSB_SPEC_COUNT_ONE(NAME, expr) +1
 constexpr int kSpecFields = 0 RSB_SPEC_FIELDS(RSB_SPEC_COUNT_ONE);
