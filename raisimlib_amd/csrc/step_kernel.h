@@ -46,6 +46,7 @@
 #include "step_math.h"      // vectors, spatial algebra, LDS access
 #include "step_terrain.h"   // sphere x height map narrow phase
 #include "step_slip.h"      // slip case of the one-contact rule, DPP row reductions
+#include "step_slip_pk.h"   // ... its packed fp32 form (step_spec.h: RSB_PK_CLASS)
 #include "stage_bodies.h"   // the in-repo action stages' per-block bodies (resident closed-loop classes)
 
 // The resident classes (kernel class bit 64) wrap the sub-step loop and the epilogue in a loop over control steps.  The wrapper is PREPROCESSOR-selected

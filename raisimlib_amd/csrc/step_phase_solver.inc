@@ -80,6 +80,14 @@
         sc.a0 = Gii[8]; sc.a1 = mu * Gii[6]; sc.a2 = mu * Gii[7];
         sc.n01 = mu * Gii[0]; sc.n02 = mu * Gii[1]; sc.n11 = mu * Gii[3]; sc.n12 = mu * Gii[4];
         sc.n00 = sc.n10 = sc.vn = sc.ls0 = sc.ls1 = 0.f;
+#if RSB_PK_SOLVE
+        // packed form (step_spec.h, step_slip_pk.h): the own block as the column pairs (G0,G3) (G1,G4) (G2,G5) - the pairs the row-block layout stores - and row 2,
+        // its inverse's rows 0 | 1 likewise, mu * G_tt as (n01,n11) (n02,n12)
+        static_assert(!TRI && !COUL, "the packed sweep is the quadruped's energy-rule classes'");
+        const f32x2 gcp[3] = {f32x2{Gii[0], Gii[3]}, f32x2{Gii[1], Gii[4]}, f32x2{Gii[2], Gii[5]}};
+        const f32x2 gip[3] = {f32x2{Ginv[0], Ginv[3]}, f32x2{Ginv[1], Ginv[4]}, f32x2{Ginv[2], Ginv[5]}};
+        const f32x2 mg1 = pk_splat(mu) * gcp[0], mg2 = pk_splat(mu) * gcp[1];
+#endif
         float lam_best[3] = {0.f, 0.f, 0.f}, best_rel = 3e38f;   // calmest iterate (returned when the solve does not converge)
         float sdx = 0.f, sdy = 0.f;   // friction direction of this contact (|.| = 1 once set)
         int sdst = 0;                 // 0: none, 1: found in this solve, 3: inherited from the previous integrate() (warm state), unused so far
@@ -310,6 +318,9 @@
 #endif
         asm volatile(".p2align 5");
         static_for<0, (TRI ? RSB_X_ALIGN_SWEEP_TRI : RSB_X_ALIGN_SWEEP)>([&](auto) { asm volatile("s_nop 0"); });
+#if RSB_PK_CLASS
+        asm volatile("; rsb sweep begin");     // (tests/test_pk_solve_host.py counts between the comment lines)
+#endif
         for (int it = 0; it < max_iter; ++it) {
           // lagged directions: a usable direction of this solve is no longer refreshed.  Two wave-uniform tests picked per env by a
           // lane mask (scalar work: the sweep loop has no vector register to spare)
@@ -322,8 +333,14 @@
             if (PROF && a.prof) ++p_solves;
             // v holds the velocity WITH the own impulse: lam_stick = lam - G_ii^-1 v, v_n without it = v_n - G_ii[n,:] lam
             float ls[3];
+#if RSB_PK_SOLVE
+            const f32x2 ls01 = pk_stick(gip, f32x2{v[0], v[1]}, v[2], f32x2{lam[0], lam[1]});
+            ls[0] = ls01.x; ls[1] = ls01.y;
+            ls[2] = fmaf(-Ginv[8], v[2], fmaf(-Ginv[7], v[1], fmaf(-Ginv[6], v[0], lam[2])));
+#else
             RSB_UNROLL for (int rr = 0; rr < 3; ++rr)
               ls[rr] = fmaf(-Ginv[3 * rr + 2], v[2], fmaf(-Ginv[3 * rr + 1], v[1], fmaf(-Ginv[3 * rr], v[0], lam[rr])));
+#endif
             const float vexn = fmaf(-Gii[8], lam[2], fmaf(-Gii[7], lam[1], fmaf(-Gii[6], lam[0], v[2])));
             const bool open = vexn > 0.f;
             const bool stick = (!open) & (ls[2] >= 0.f) & (fmaf(ls[1], ls[1], ls[0] * ls[0]) <= (mu2 * ls[2]) * ls[2]);
@@ -343,6 +360,11 @@
 #endif
               SlipCoef kc;
               kc = sc;
+#if RSB_PK_SOLVE
+              SlipCoefPk kp;
+              pk_coef(kp, sc.a0, sc.a1, sc.a2, gcp[2], mg1, mg2, pk_vex(gcp, f32x2{v[0], v[1]}, f32x2{lam[0], lam[1]}, lam[2]), vexn, ls01);
+              kc = slip_unpack(kp);      // (the serial scan, the quad scan and the global search read the scalar record: the same registers)
+#else
               {
                 const float vex0 = v[0] - (Gii[0] * lam[0] + Gii[1] * lam[1] + Gii[2] * lam[2]);
                 const float vex1 = v[1] - (Gii[3] * lam[0] + Gii[4] * lam[1] + Gii[5] * lam[2]);
@@ -350,10 +372,15 @@
                 kc.n10 = sc.a0 * vex1 - vexn * Gii[5]; kc.n11 = sc.a1 * vex1 - vexn * sc.n11; kc.n12 = sc.a2 * vex1 - vexn * sc.n12;
                 kc.vn = vexn; kc.ls0 = ls[0]; kc.ls1 = ls[1];
               }
+#endif
               // one guarded Newton step on every lane (the common case; lanes without a candidate ignore the result)
               if (PROF && a.prof) ++p_newton;
               float nx, ny, dstep;
+#if RSB_PK_SOLVE
+              bool ok = slip_newton_pk(kp, mu, sdx, sdy, nx, ny, dstep) & need & (sdst != 0) & (refine != 0);
+#else
               bool ok = slip_newton<COUL>(kc, mu, sdx, sdy, nx, ny, dstep) & need & (sdst != 0) & (refine != 0);
+#endif
 #ifdef RSB_X_STAMP_BASIN   /* (profiling twins, RSB_PROF_FINE: the basin-check block is charged to the `magnitude + dl` accumulator instead of the refresh's) */
               lap(t_newt);
 #endif
@@ -433,14 +460,28 @@
             const float lnn = -vexn * __builtin_amdgcn_rcpf(fmaxf(den, kDenMin * sc.a0));
             const float ltn = mu * lnn;
             float ln[3];
+            float dl[3];
+#if RSB_PK_SOLVE
+            {
+              const f32x2 lt = pk_splat(ltn) * f32x2{sdx, sdy};
+              ln[0] = slip ? lt.x : (stick ? ls[0] : 0.f);
+              ln[1] = slip ? lt.y : (stick ? ls[1] : 0.f);
+              ln[2] = slip ? lnn : (stick ? ls[2] : 0.f);
+              const f32x2 l01 = f32x2{lam[0], lam[1]}, df = pk_splat(alpha) * (f32x2{ln[0], ln[1]} - l01);   // (a product of a difference: nothing to fuse)
+              dl[0] = mine ? df.x : 0.f; dl[1] = mine ? df.y : 0.f;
+              dl[2] = mine ? alpha * (ln[2] - lam[2]) : 0.f;
+              const f32x2 ln01 = l01 + f32x2{dl[0], dl[1]};
+              lam[0] = ln01.x; lam[1] = ln01.y; lam[2] += dl[2];
+            }
+#else
             ln[0] = slip ? ltn * sdx : (stick ? ls[0] : 0.f);
             ln[1] = slip ? ltn * sdy : (stick ? ls[1] : 0.f);
             ln[2] = slip ? lnn : (stick ? ls[2] : 0.f);
-            float dl[3];
             RSB_UNROLL for (int rr = 0; rr < 3; ++rr) {
               dl[rr] = mine ? alpha * (ln[rr] - lam[rr]) : 0.f;
               lam[rr] += dl[rr];
             }
+#endif
             lap(t_mag);
             if constexpr (AA) {
               // the last pass's exchange waits for the Anderson step (one exchange carries both changes)
@@ -512,6 +553,9 @@
             exchange(dl_last, unused);   // the last pass's changes + the Anderson step's
           }
         }
+#if RSB_PK_CLASS
+        asm volatile("; rsb sweep end");
+#endif
         if (PROF && pfine) tz0 = t_prev;
         if (!converged) { flag |= 4; lam[0] = lam_best[0]; lam[1] = lam_best[1]; lam[2] = lam_best[2]; }
         if (__any(nselfc > 0)) {   // the second entry of a self-collision carries the first one's impulse (in its opposite frame)

@@ -176,6 +176,31 @@ static_assert(kFlatSink >= 6 + RSB_SPEC_DEPTH - 1 && kFlatSink < kFlatCw, "flat 
 }  // namespace rsbk
 #endif
 
+// Packed fp32 form of the contact solve's arithmetic, in the specialised code objects of the quadruped classes (16 lanes per env, eight contact slots or fewer, the
+// energy slip rule: lock-step, pipelined, resident and closed-loop).  Such a launch is one wave per SIMD, and a lone wave pays ~4 cycles for every VALU instruction
+// it issues whatever the instruction does (profiles/r02_ubench_lone_wave_latency.txt), so two fp32 operations that share an operand pattern are written as ONE
+// v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32 on a register pair, as the impulse exchange already does.  The packed instructions round each half as their scalar
+// twins do; which products are fused is written out with explicit FMAs, read off the assembly of the scalar form (step_slip_pk.h), so the results are the same bits.
+// What is packed is the sweep loop (step_phase_solver.inc): the own block is held as the column pairs (G0,G3) (G1,G4) (G2,G5) - the pairs the row-block layout
+// stores - and row 2, its inverse's rows 0 | 1 likewise, mu * G_tt as (n01,n11) (n02,n12); the stick impulse ls[0|1], the tangential velocity vex0|vex1 and the
+// coefficients kc.n0k|n1k of a direction refresh, the Newton step's N0|N1, dN0|dN1, (P, Q) and the two sums of h', the rotation with its normalisation, the energy
+// check's vt0|vt1 and products, and the impulse update ln|dl|lam[0|1] are pairs.  den, mdp, h, the reciprocals, the guards and every select stay scalar.
+// (Two more parts were built and are not here: the quad basin scan through the packed slip_E put the resident class 40 bytes into scratch, and the Delassus
+//  accumulation on pairs measured nothing - DESIGN.md section 9.)
+// -DRSB_X_NO_PK_SOLVE compiles the scalar instructions: same results bit for bit (tests/test_gpu_pk_solve.py).  RSB_PK_CLASS marks the code objects the form applies
+// to, switch or not: they carry the comment lines `; rsb sweep begin/end` in their assembly (tests/test_pk_solve_host.py counts between them).  The ahead-of-time
+// classes, the humanoid (KMAX 16) and the Coulomb classes (| 32) compile what they compiled.
+#if defined(RSB_SPECIALIZED) && defined(RSB_I_LPE) && (RSB_I_LPE) == 16 && (RSB_I_KMAX) <= 8 && !((RSB_I_CL) & 32)
+#define RSB_PK_CLASS 1
+#else
+#define RSB_PK_CLASS 0
+#endif
+#if RSB_PK_CLASS && !defined(RSB_X_NO_PK_SOLVE)
+#define RSB_PK_SOLVE 1
+#else
+#define RSB_PK_SOLVE 0
+#endif
+
 namespace rsbk {
 #define RSB_SPEC_COUNT_ONE(NAME, expr) +1
 constexpr int kSpecFields = 0 RSB_SPEC_FIELDS(RSB_SPEC_COUNT_ONE);
