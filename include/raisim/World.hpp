@@ -273,6 +273,31 @@ class BatchedWorld {
     std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
     RSB_CHECK(rsb_imu_observe(world_, frames.data(), (int)frames.size(), udot, out, rowStride, RSB_HOST));
   }
+  /// What a loop over ArticulatedSystem::getContacts() adds up per link, for ALL envs in one call, on the device, from the contact list of the last
+  /// sub-step (staged view rows are uploaded first): force [N,F,3] the net contact force on the frame's body (every record as impulse / getTimeStep()),
+  /// torque [N,F,3] its moment about the frame's point, count [N,F] the records that act on the body; any may be null (not all).  World frame; local:
+  /// in the axes of the frame's body (R^T x); includeSelf = false leaves self-collision records out.
+  void getBodyContactWrenches(const std::vector<rsb_frame>& frames, bool local, bool includeSelf, float* force, float* torque, int32_t* count) {
+    std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
+    RSB_CHECK(rsb_get_body_contact_wrenches(world_, frames.data(), (int)frames.size(), (local ? RSB_CONTACT_LOCAL : 0) | (includeSelf ? 0 : RSB_CONTACT_NO_SELF), force,
+                                            torque, count, RSB_HOST));
+  }
+  /// The contact rows of an observation for all envs: out[e * rowStride + 6 f + 0..5] = (contact flag: normal force > forceThreshold; net force 1..3, the
+  /// bits of getBodyContactWrenches; normal force; slip speed).  rowStride in floats, 0 = 6 F; a larger one leaves the other columns of a row alone.
+  void getContactReadings(const std::vector<rsb_frame>& frames, float forceThreshold, bool local, bool includeSelf, float* out, long long rowStride = 0) {
+    std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
+    RSB_CHECK(rsb_contact_observe(world_, frames.data(), (int)frames.size(), (local ? RSB_CONTACT_LOCAL : 0) | (includeSelf ? 0 : RSB_CONTACT_NO_SELF), forceThreshold, out,
+                                  rowStride, RSB_HOST));
+  }
+  /// Feet air time / contact time in the caller's [N,F] buffers, one update per control step of length dt: reset (resetMask[e] != 0, may be null) -> all
+  /// zero; contact (the flag above) -> touchdown = the old airTime, airTime = 0, contactTime += dt; else touchdown = 0, airTime += dt, contactTime = 0.
+  /// Either timer may be null (not both), touchdown may be null.
+  void updateContactTimers(const std::vector<rsb_frame>& frames, float forceThreshold, float dt, const uint8_t* resetMask, float* airTime, float* contactTime,
+                           float* touchdown, bool includeSelf = true) {
+    std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
+    RSB_CHECK(rsb_contact_timers(world_, frames.data(), (int)frames.size(), includeSelf ? 0 : RSB_CONTACT_NO_SELF, forceThreshold, dt, resetMask, airTime, contactTime,
+                                 touchdown, RSB_HOST));
+  }
   /// setExternalForce / setExternalTorque for all envs: adds J^T force[e] + Jrot^T torque[e] (world frame, [N,3] each, either may be null)
   /// to the feed-forward row of every env with mask[e] != 0 (null: all).  Same lifetime as the per-env calls: until setGeneralizedForce / clearExternalForces.
   void addExternalWrench(const rsb_frame& frame, const float* force, const float* torque, const uint8_t* mask = nullptr) {

@@ -43,6 +43,7 @@
  *                                          in one call                                (HeightMap.hpp, World.hpp, absent)
  *   rsb_ray_cast / rsb_ray_scan         <- World::rayTest against the terrain AND the robot's collision bodies, and (new) its fused
  *                                          sensor form: a depth camera or lidar mounted on a body, for all envs in one call
+ *   rsb_get_body_contact_wrenches / rsb_contact_observe / rsb_contact_timers <- the host loop over ArticulatedSystem::getContacts(), for all envs in one call
  *   rsb_gather_obs                      <- (new) the (q, u, contact-force) observation block that
  *                                          VectorizedEnvironment::observe() is built from
  *   rsb_env_observe_normalized / rsb_env_get_obs_stats / rsb_env_set_obs_stats
@@ -472,6 +473,54 @@ int rsb_ray_cast(rsb_world* w, const float* origins, const float* directions, in
  * depend on which other frames or directions the call lists. */
 int rsb_ray_scan(rsb_world* w, const rsb_frame* frames, int n_frames, const float* dirs, int n_points, int flags, float max_dist,
                  float* out, long long row_stride, int32_t* hit, int space);
+
+/* Contact sensors of ALL envs in one call, from the resident contact list [RECALL upstream's per-object answer: a host loop over
+ * ArticulatedSystem::getContacts()]: one HIP kernel on the world's stream, like the queries above (a pipelined world is joined first); the RSB_DEVICE
+ * forms do not synchronise, the RSB_HOST forms stage through the same device buffer.  frames as in rsb_get_frame_kinematics (a HOST array).  None of
+ * the three changes a bit of the world.  An error touches no output.
+ *
+ * A "record" is an entry c < min(count[e], kmax) of env e's resident contact list (RSB_F_CONTACTS / RSB_F_CONTACT_COUNT, what rsb_get_contacts
+ * returns: the last sub-step's).  It acts as the world force impulse / rsb_get_timestep() at `position` on body `body`, the convention of
+ * RSB_DYN_CONTACTS; inv_dt = (float)(1.0 / dt).  Frame f OWNS the records whose body == frames[f].body: every primitive of the link, second-flank
+ * and capsule entries, and its entry of a self-collision.  flags: RSB_CONTACT_LOCAL - vector outputs multiplied by R^T (the axes of the frame's body,
+ * R = rot of rsb_get_frame_kinematics); RSB_CONTACT_NO_SELF - records flagged RSB_CONTACT_SELF_A / _B are left out.  Sums run in ascending record
+ * index in registers: no atomics, the same bits in every call, for any N, any other frames listed, any subset of outputs, host or device buffers.
+ *
+ * rsb_get_body_contact_wrenches: force [N,F,3] = sum of the owned records' forces; torque [N,F,3] = sum of (position_c - p_f) x force_c, p_f the
+ * frame's world point (pos of rsb_get_frame_kinematics); count [N,F] int32 = number of owned records.  Any output may be NULL, not all.
+ *
+ * rsb_contact_observe: the fused contact rows of an observation, six floats for env e and frame f at out[e * row_stride + 6 f + 0..5]:
+ *   0     1.0f if the normal force (column 4) is greater than force_threshold, else 0.0f
+ *   1..3  the net force: the bits of rsb_get_body_contact_wrenches' force under the same flags
+ *   4     the normal force, sum_c (impulse_c . normal_c) * inv_dt
+ *   5     the slip speed, max_c |v - (v . n_c) n_c| with v = v_b + omega_b x (position_c - p_b) the velocity of the body's material point at the
+ *         record's position from the resident gv; 0 without an owned record; the same under RSB_CONTACT_LOCAL
+ * row_stride as in rsb_imu_observe: 0 = 6 F; a larger value writes columns [0, 6 F) of rows of that pitch and touches no other float; a smaller
+ * non-zero value is RSB_E_INVALID.
+ *
+ * rsb_contact_timers: feet air time / contact time in the CALLER's buffers (the world stores nothing), one fp32 update per (env, frame) with
+ * "contact" the predicate of column 0 above and dt the caller's control step (positive, finite):
+ *   reset_mask[e] != 0    touchdown = 0               air_time = 0     contact_time = 0
+ *   contact               touchdown = old air_time    air_time = 0     contact_time += dt
+ *   no contact            touchdown = 0               air_time += dt   contact_time = 0
+ * (touchdown: the flight that just ended, 0 if there was none.)  A timer that is NULL is taken as 0 and not written.
+ *
+ * Fixed-base models: body 0 does not move, whatever the base rows of gv hold - no bit of them matters.
+ * RSB_E_INVALID, with a message naming the function: a null world; a bad `space`; every output NULL; n_frames outside 1..RSB_MAX_FRAMES, a frame
+ * whose body is out of range or whose offset is not finite; unknown flag bits; a negative or non-finite force_threshold; a bad row_stride; a bad dt. */
+int rsb_get_body_contact_wrenches(rsb_world* w, const rsb_frame* frames, int n_frames, int flags,
+                                  float* force,         /* [N,F,3] */
+                                  float* torque,        /* [N,F,3] */
+                                  int32_t* count,       /* [N,F]    any output may be NULL, not all */
+                                  int space);
+int rsb_contact_observe(rsb_world* w, const rsb_frame* frames, int n_frames, int flags, float force_threshold,
+                        float* out, long long row_stride, int space);
+int rsb_contact_timers(rsb_world* w, const rsb_frame* frames, int n_frames, int flags, float force_threshold, float dt,
+                       const uint8_t* reset_mask,       /* [N] or NULL: envs whose timers restart (the done flags of a step) */
+                       float* air_time,                 /* [N,F] in/out */
+                       float* contact_time,             /* [N,F] in/out; either timer may be NULL, not both */
+                       float* touchdown,                /* [N,F] out, may be NULL */
+                       int space);
 
 /* obs block [N, nq+nv+3*n_force_slots] = (q, u, contact force on chosen collision primitives).
  * collision_indices: host array of n_force_slots collision-primitive indices (e.g. the feet);

@@ -56,6 +56,7 @@ RSB_MAX_RAY_POINTS = 4096
 RSB_RAY_BODIES, RSB_RAY_OWN_BODY, RSB_RAY_PLANAR, RSB_RAY_MISS_MAX = 1, 2, 4, 8
 RSB_RAY_HIT_NONE, RSB_RAY_HIT_TERRAIN = -1, -2
 RSB_ACC_LOCAL, RSB_ACC_PROPER = 1, 2
+RSB_CONTACT_LOCAL, RSB_CONTACT_NO_SELF = 1, 2
 
 
 class TerrainProperties(C.Structure):
@@ -218,6 +219,9 @@ PROTOTYPES = {
     "rsb_ray_test": (_I, [_VP, _FP, _FP, _I, C.c_float, _FP, _I]),
     "rsb_ray_cast": (_I, [_VP, _FP, _FP, _I, C.c_float, _I, _FP, _VP, _I]),
     "rsb_ray_scan": (_I, [_VP, C.POINTER(Frame), _I, _FP, _I, _I, C.c_float, _FP, C.c_longlong, _VP, _I]),
+    "rsb_get_body_contact_wrenches": (_I, [_VP, C.POINTER(Frame), _I, _I, _FP, _FP, _VP, _I]),
+    "rsb_contact_observe": (_I, [_VP, C.POINTER(Frame), _I, _I, C.c_float, _FP, C.c_longlong, _I]),
+    "rsb_contact_timers": (_I, [_VP, C.POINTER(Frame), _I, _I, C.c_float, C.c_float, _VP, _FP, _FP, _FP, _I]),
     "rsb_obs_dim": (_I, [_VP, _I]),
     "rsb_gather_obs": (_I, [_VP, _FP, _FP, _I, _I]),
     "rsb_reset_terminated": (_I, [_VP, _FP, _I, _FP, _FP, _I, _FP, _I]),

@@ -40,6 +40,7 @@ HOST_SOURCES = {   # source -> headers it depends on
     "rsb_centroidal.hip": _WORLD_DEPS + ["frames_chain.h"],  # batched centre of mass, momentum, energy and the centroidal momentum matrix
     "rsb_dynamics.hip": _WORLD_DEPS + ["frames_chain.h"],    # batched inverse dynamics with joint reaction wrenches, contact-free forward dynamics
     "rsb_frame_accel.hip": _WORLD_DEPS + ["frames_chain.h"], # batched frame accelerations, frame Jacobian rates and IMU readings
+    "rsb_contact_sensor.hip": _WORLD_DEPS + ["frames_chain.h"],   # batched contact sensors: body wrenches, contact rows of an observation, feet air time
     "rsb_spec.hip": _WORLD_DEPS,      # specialised code objects of the step kernel: key, cache directory, compile, load, launch
 }
 # the fused step kernel: the template's skeleton (step_kernel.h), its device helpers (step_math / step_terrain / step_slip .h) and its body, one

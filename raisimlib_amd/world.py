@@ -583,6 +583,101 @@ class BatchedWorld:
         check(self.L.rsb_imu_observe(self.handle, arr, F, ud, optr, stride, space), "rsb_imu_observe")
         return out
 
+    # -- contact sensors: body wrenches, the contact rows of an observation, feet air time (rsb_contact_sensor.hip) ------
+    @staticmethod
+    def _contact_flags(local, include_self):
+        return (_capi.RSB_CONTACT_LOCAL if local else 0) | (0 if include_self else _capi.RSB_CONTACT_NO_SELF)
+
+    def _sensor_buffer(self, what, name, v, dtype, count, device):
+        """one caller-owned buffer of a contact-sensor call (None: not asked for) -> its C argument: a contiguous torch CUDA tensor (device) or a
+        C-contiguous numpy array"""
+        if v is None:
+            return None
+        if device:
+            if not (self._is_torch(v) and v.is_cuda and v.is_contiguous() and str(v.dtype) == f"torch.{dtype}" and v.numel() == count and v.device.index == self.device):
+                raise ValueError(f"{what}: {name} must be a contiguous {dtype} CUDA tensor of {count} elements on cuda:{self.device}")
+            return C.c_void_p(v.data_ptr())
+        if not (isinstance(v, np.ndarray) and v.dtype == np.dtype(dtype) and v.flags.c_contiguous and v.size == count):
+            raise ValueError(f"{what}: {name} must be a C-contiguous {dtype} array of {count} elements")
+        return _hp(v)
+
+    def body_contact_wrenches(self, frames, local=False, include_self=True, force=True, torque=False, count=False, out=None):
+        """The net contact wrench on the body of each frame, from the resident contact list (what get_contacts returns), for every env at once ->
+        {"force": [N, F, 3], "torque": [N, F, 3], "count": [N, F] int32}, the outputs asked for only.  A frame owns the records of its body; a
+        record acts as impulse / timestep at its position (the convention of inverse_dynamics(contacts=True)).  force: the sum of the owned
+        records' forces; torque: their moment about the frame's point; count: how many there are.  World axes; local=True: the axes of the
+        frame's body (R^T x).  include_self=False leaves self-collision records out.  out: {name: torch CUDA tensor} (RSB_DEVICE, no
+        synchronisation; count as int32) or {name: numpy array}; None: fresh host arrays."""
+        what = "body_contact_wrenches"
+        arr, n = self._frames(frames)
+        names = ("force", "torque", "count")
+        dtypes = {"force": "float32", "torque": "float32", "count": "int32"}
+        sizes = {"force": self.N * n * 3, "torque": self.N * n * 3, "count": self.N * n}
+        if out is None:
+            want = dict(force=force, torque=torque, count=count)
+            out = {k: np.empty((self.N, n, 3) if k != "count" else (self.N, n), dtypes[k]) for k in names if want[k]}
+        if not out:
+            raise ValueError(f"{what}: no output asked for")
+        if set(out) - set(names):
+            raise ValueError(f"{what}: unknown outputs {sorted(set(out) - set(names))}")
+        torch_like = [self._is_torch(v) for v in out.values()]
+        if any(torch_like) != all(torch_like):
+            raise ValueError(f"{what}: outputs must be all torch tensors or all numpy arrays")
+        ptrs = [self._sensor_buffer(what, k, out.get(k), dtypes[k], sizes[k], torch_like[0]) for k in names]
+        check(self.L.rsb_get_body_contact_wrenches(self.handle, arr, n, self._contact_flags(local, include_self), *ptrs,
+                                                   RSB_DEVICE if torch_like[0] else RSB_HOST), "rsb_get_body_contact_wrenches")
+        return out
+
+    def contact_observe(self, frames, threshold=1.0, local=False, include_self=True, out=None, row_stride=0):
+        """The contact rows of an observation: [N, F, 6], out[e, f] = (contact flag: 1 where the normal force exceeds `threshold` [N], else 0; the
+        net force on the frame's body, the bits of body_contact_wrenches' force; the normal force sum (impulse . normal) / timestep; the slip
+        speed: the largest tangential speed of the body's material point at an owned record).  local / include_self as in
+        body_contact_wrenches.  row_stride (floats, 0 = 6 F): with a larger value `out` is the first contact column of a wider [N, row_stride]
+        buffer - a torch view such as obs[:, k:] (only its data pointer is used) or a numpy array of N * row_stride floats - whose other columns
+        are left alone.  A torch `out` means RSB_DEVICE, no synchronisation."""
+        arr, F = self._frames(frames)
+        width = 6 * F
+        stride = int(row_stride) or width
+        flags = self._contact_flags(local, include_self)
+        if stride == width:
+            space, ptrs, res = self._frame_outputs(("out",), dict(out=True), {"out": (self.N, F, 6)}, None if out is None else {"out": out}, "contact_observe")
+            check(self.L.rsb_contact_observe(self.handle, arr, F, flags, float(threshold), ptrs[0], 0, space), "rsb_contact_observe")
+            return res["out"]
+        if out is None:
+            raise ValueError("contact_observe: a row_stride needs `out`")
+        if self._is_torch(out):
+            if not (out.is_cuda and str(out.dtype) == "torch.float32" and out.device.index == self.device):
+                raise ValueError(f"contact_observe: out must be a float32 CUDA tensor on cuda:{self.device}")
+            space, optr = RSB_DEVICE, C.c_void_p(out.data_ptr())
+        else:
+            if not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.flags.c_contiguous and (stride < width or out.size >= (self.N - 1) * stride + width)):
+                raise ValueError("contact_observe: out must be a C-contiguous float32 array that holds N rows of row_stride floats")
+            space, optr = RSB_HOST, _hp(out)
+        check(self.L.rsb_contact_observe(self.handle, arr, F, flags, float(threshold), optr, stride, space), "rsb_contact_observe")
+        return out
+
+    def contact_timers(self, frames, dt, air_time, contact_time=None, touchdown=None, reset_mask=None, threshold=1.0, include_self=True):
+        """Feet air time / contact time, kept in the caller's [N, F] float32 buffers and updated in place, once per control step of length dt:
+        where reset_mask[e] != 0 (uint8 [N], e.g. the done flags) all three restart at 0; in contact (the flag of contact_observe)
+        touchdown = the old air_time (the flight that just ended), air_time = 0, contact_time += dt; otherwise touchdown = 0, air_time += dt,
+        contact_time = 0.  Either timer may be None, not both; touchdown is an output only.  All torch CUDA tensors (RSB_DEVICE, no
+        synchronisation) or all numpy arrays.  -> (air_time, contact_time, touchdown)"""
+        what = "contact_timers"
+        arr, n = self._frames(frames)
+        given = [x for x in (air_time, contact_time, touchdown, reset_mask) if x is not None]
+        if air_time is None and contact_time is None:
+            raise ValueError(f"{what}: air_time and contact_time are both None")
+        torch_like = [self._is_torch(x) for x in given]
+        if any(torch_like) != all(torch_like):
+            raise ValueError(f"{what}: the buffers must be all torch tensors or all numpy arrays")
+        dev = torch_like[0]
+        pairs = self.N * n
+        ptrs = [self._sensor_buffer(what, "reset_mask", reset_mask, "uint8", self.N, dev), self._sensor_buffer(what, "air_time", air_time, "float32", pairs, dev),
+                self._sensor_buffer(what, "contact_time", contact_time, "float32", pairs, dev), self._sensor_buffer(what, "touchdown", touchdown, "float32", pairs, dev)]
+        check(self.L.rsb_contact_timers(self.handle, arr, n, self._contact_flags(False, include_self), float(threshold), float(dt), *ptrs,
+                                        RSB_DEVICE if dev else RSB_HOST), "rsb_contact_timers")
+        return air_time, contact_time, touchdown
+
     def add_external_wrench(self, frame, force=None, torque=None, mask=None):
         """setExternalForce / setExternalTorque of every env at once: tau_ff[e] += J_lin(e)^T force[e] + J_rot(e)^T torque[e] at the current state
         for the envs with mask[e] != 0 (None: all).  force / torque [N, 3] world frame, mask [N] uint8: numpy arrays, or torch CUDA tensors (no
