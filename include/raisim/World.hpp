@@ -338,6 +338,21 @@ class BatchedWorld {
     RSB_CHECK(rsb_forward_dynamics(world_, tau, frames.empty() ? nullptr : frames.data(), (int)frames.size(), force, torque, contacts ? RSB_DYN_CONTACTS : 0, udot,
                                    RSB_HOST));
   }
+  /// X [N,R,dof()] = (M(q) + diag(jointDiag))^-1 B for ALL envs in one call, on the device, at the resident configuration, without the dense
+  /// getInverseMassMatrix(): one articulated-body factorisation per env, two tree passes per column.  Host buffers; X may be B.  jointDiag [dof()]
+  /// (null: zeros): non-negative, zero on a floating base's six entries; dt (kd + dt kp) gives the effective mass the contact problem sees.
+  /// A fixed base: the joint block is solved, the six base rows of X are zero.
+  void applyInverseMass(const float* B, int nRhs, const float* jointDiag, float* X) {
+    std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
+    RSB_CHECK(rsb_apply_inverse_mass(world_, B, nRhs, jointDiag, X, RSB_HOST));
+  }
+  /// The operational-space matrices at frames (at most RSB_MAX_DELASSUS_FRAMES) for all envs: JMinv [N,kF,dof()] = J (M + D)^-1 and G [N,kF,kF] =
+  /// J (M + D)^-1 J^T, J the stacked rows of getFrameJacobians - k = 3 rows per frame (Jlin), with angular k = 6 (Jlin, then Jrot).  Either may be
+  /// null.  G equals its transpose bit for bit and may be singular; its inverse, the operational-space inertia, is the caller's to take.
+  void getFrameDelassus(const std::vector<rsb_frame>& frames, bool angular, const float* jointDiag, float* G, float* JMinv) {
+    std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
+    RSB_CHECK(rsb_get_frame_delassus(world_, frames.data(), (int)frames.size(), angular ? RSB_DELASSUS_ANGULAR : 0, jointDiag, G, JMinv, RSB_HOST));
+  }
 
   /// HeightMap::getHeight / getNormal for ALL envs in one call, on the device, each env on its own terrain: xy [N,P,2] world coordinates ->
   /// height [N,P], normal [N,P,3] (unit normal of the triangle under the point; either may be null).  Coordinates outside the map are clamped to it;

@@ -38,6 +38,9 @@
  *   rsb_inverse_dynamics / rsb_forward_dynamics
  *                                       <- ArticulatedSystem::setComputeInverseDynamics / getForceAtJointInWorldFrame /
  *                                          getTorqueAtJointInWorldFrame, and the plain equations of motion, for all envs in one call
+ *   rsb_apply_inverse_mass / rsb_get_frame_delassus
+ *                                       <- (new) M^-1 B and the operational-space matrices J M^-1, J M^-1 J^T at chosen frames, for all
+ *                                          envs in one call, without the dense getInverseMassMatrix()
  *   rsb_get_terrain_height / rsb_height_scan / rsb_ray_test
  *                                       <- HeightMap::getHeight / getNormal, World::rayTest (against the terrain), for all envs
  *                                          in one call                                (HeightMap.hpp, World.hpp, absent)
@@ -407,6 +410,44 @@ int rsb_forward_dynamics(rsb_world* w,
                          const rsb_frame* frames, int n_frames, const float* force, const float* torque, int flags,
                          float* udot,                  /* [N,nv]                                                         */
                          int space);
+
+/* M(q)^-1 applied to what the caller chooses, for ALL envs in one call, without forming M: the articulated-body factorisation of rsb_forward_dynamics
+ * is done once per env, then every column costs one force and one acceleration pass over the tree (O(nb)).  HIP kernels on the world's stream, like
+ * the queries above (a pipelined world is joined first); the RSB_DEVICE forms do not synchronise, the RSB_HOST forms stage through the same device
+ * buffer.  Both read the resident gc ONLY (the base quaternion normalised first): gv, gravity, PD, damping, effort clips and joint limits do not
+ * enter.  Neither changes a bit of the world.  An error touches no output.
+ *
+ * Convention: that of rsb_get_mass_matrix - gv order base linear, base angular, joints; M carries the armature on its diagonal.
+ * joint_diag: HOST array [nv] or NULL (zeros), D = diag(joint_diag) is added to M: non-negative finite entries, added to the joints' diagonal exactly
+ * where the armature is; the six base entries of a floating base must be 0.  With d = dt (kd + dt kp) on the joints, M + D is the effective mass the
+ * step's contact problem sees under PD control.
+ *
+ * rsb_apply_inverse_mass:  X[e,r,:] = (M(q_e) + D)^-1 B[e,r,:] for r < n_rhs (1..RSB_MAX_DOF).  X == B is allowed and gives the same bits.
+ * rsb_get_frame_delassus:  with J the stacked rows of rsb_get_frame_jacobians - row 3f+a is the row of J_lin of frame f along world axis a; with
+ *   RSB_DELASSUS_ANGULAR row 6f+a is that row for a < 3 and the row of J_rot along axis a-3 for a >= 3 - and k = 3 or 6 rows per frame:
+ *     JMinv [N,kF,nv] = J (M + D)^-1          G [N,kF,kF] = J (M + D)^-1 J^T          either may be NULL, not both.
+ *   G[e] equals its transpose bit for bit: entries (i,j) and (j,i) both carry the value computed for i <= j - it is what a Cholesky routine is
+ *   handed.  G may be singular (more rows than the frames' chains have degrees of freedom); inverting it is the caller's choice.
+ *   frames as in rsb_get_frame_kinematics (a HOST array), n_frames 1..RSB_MAX_DELASSUS_FRAMES.
+ * Arithmetic: the factorisation (chain walk, inertias, articulated-inertia pass, the base's LDL^T) runs once per env in double, the column passes
+ * in float; inputs and outputs are float32.  No atomics; env e's results depend on env e's rows alone - the same bits for any N and any outputs.
+ * Fixed-base models: the convention of rsb_get_inverse_mass_matrix - the joint block is solved; the six base rows of X and the six base columns of
+ * JMinv are zero; no bit of the base entries of B and joint_diag matters.
+ * RSB_E_INVALID, with a message naming the function: a null world; a bad `space`; n_rhs or n_frames out of range; B or X NULL, or every output NULL;
+ * a frame whose body is out of range or whose offset is not finite; unknown flag bits; a joint_diag entry that is negative or not finite, or a
+ * non-zero base entry of a floating base. */
+int rsb_apply_inverse_mass(rsb_world* w,
+                           const float* B,               /* [N,R,nv] in `space`                                          */
+                           int n_rhs,                    /* R, 1..RSB_MAX_DOF                                            */
+                           const float* joint_diag,      /* HOST [nv] or NULL                                            */
+                           float* X,                     /* [N,R,nv] in `space`; X == B allowed                          */
+                           int space);
+int rsb_get_frame_delassus(rsb_world* w, const rsb_frame* frames, int n_frames, /* 1..RSB_MAX_DELASSUS_FRAMES */
+                           int flags,                    /* RSB_DELASSUS_ANGULAR                                         */
+                           const float* joint_diag,      /* HOST [nv] or NULL                                            */
+                           float* G,                     /* [N,kF,kF], k = 3 or 6                                        */
+                           float* JMinv,                 /* [N,kF,nv]; either output may be NULL, not both               */
+                           int space);
 
 /* Terrain queries of ALL envs in one call [RECALL upstream's per-object HeightMap::getHeight / getNormal and World::rayTest, called per env on the
  * host]: HIP kernels on the world's stream, like the frame queries above; the RSB_DEVICE forms do not synchronise, the RSB_HOST forms stage through

@@ -135,6 +135,10 @@ typedef enum rsb_scan_mode {
 /* Dynamics queries (rsb_inverse_dynamics, rsb_forward_dynamics; rsb.h): bits of their `flags` argument */
 #define RSB_DYN_CONTACTS 1        /* bit 0: the resident contact list acts, each record as the world force impulse / dt at its position on its body */
 
+/* Inverse-mass queries (rsb_apply_inverse_mass, rsb_get_frame_delassus; rsb.h) */
+#define RSB_DELASSUS_ANGULAR 1        /* flags bit 0: six rows per frame (linear 0..2, angular 3..5) instead of three */
+#define RSB_MAX_DELASSUS_FRAMES 16    /* 16 x 6 = 96 rows: G is at most 96 x 96 per env */
+
 /* Contact sensors (rsb_get_body_contact_wrenches, rsb_contact_observe, rsb_contact_timers; rsb.h): bits of their `flags` argument */
 #define RSB_CONTACT_LOCAL   1     /* vector outputs in the axes of the frame's body: R^T x, R = rot of rsb_get_frame_kinematics */
 #define RSB_CONTACT_NO_SELF 2     /* records flagged RSB_CONTACT_SELF_A / _B are left out (terrain contacts only) */

@@ -774,6 +774,56 @@ class BatchedWorld:
         check(self.L.rsb_forward_dynamics(self.handle, *args, _capi.RSB_DYN_CONTACTS if contacts else 0, ptrs[0], space), "rsb_forward_dynamics")
         return res["udot"]
 
+    # -- inverse mass: M^-1 B and the frames' Delassus matrices of every env in one call (rsb_inverse_mass.hip) -----------------------------
+    def _joint_diag(self, what, joint_diag):
+        """joint_diag [nv] or None -> (C argument, what must stay alive until the call returns): always a float32 HOST array"""
+        if joint_diag is None:
+            return None, None
+        if self._is_torch(joint_diag):
+            joint_diag = joint_diag.detach().cpu().numpy()
+        a = _host(joint_diag, np.float32)
+        if a.size != self.nv:
+            raise ValueError(f"{what}: joint_diag must hold {self.nv} elements")
+        return _hp(a), a
+
+    def apply_inverse_mass(self, B, joint_diag=None, out=None):
+        """X [N, R, nv] = (M(q) + diag(joint_diag))^-1 B for B [N, R, nv] (or [N, nv]: R = 1, X [N, nv]) at the resident configuration, in the
+        convention of get_mass_matrix, by the articulated-body factorisation: one factorisation per env, two tree passes per column, no dense M.
+        joint_diag [nv] (host; None: zeros): non-negative, zero on a floating base's six entries - dt (kd + dt kp) gives the effective mass the
+        step's contact problem sees.  A fixed base: the joint block is solved, X[..., :6] = 0.  Only gc is read; the world is left as it was.
+        out: a float32 array or a torch CUDA tensor of B's size (RSB_DEVICE, no synchronisation; B is then a torch CUDA tensor too); out may be B."""
+        cnt = int(B.numel()) if self._is_torch(B) else int(np.size(B))
+        if cnt == 0 or cnt % (self.N * self.nv):
+            raise ValueError(f"apply_inverse_mass: B must hold N * R * nv = {self.N} * R * {self.nv} elements")
+        R = cnt // (self.N * self.nv)
+        shape = (self.N, self.nv) if (B.dim() if self._is_torch(B) else np.ndim(B)) == 2 and R == 1 else (self.N, R, self.nv)
+        space, ptrs, res = self._frame_outputs(("X",), dict(X=True), {"X": shape}, None if out is None else {"X": out}, "apply_inverse_mass")
+        if space == RSB_DEVICE:
+            if not (self._is_torch(B) and B.is_cuda and B.is_contiguous() and str(B.dtype) == "torch.float32" and B.device.index == self.device):
+                raise ValueError(f"apply_inverse_mass: B must be a contiguous float32 CUDA tensor on cuda:{self.device}")
+            bp, keep = C.c_void_p(B.data_ptr()), B
+        else:
+            if self._is_torch(B):
+                raise ValueError("apply_inverse_mass: inputs and outputs must be all torch tensors or all numpy arrays")
+            keep = B if out is B else _host(B, np.float32)
+            bp = _hp(keep)
+        dp, dkeep = self._joint_diag("apply_inverse_mass", joint_diag)
+        check(self.L.rsb_apply_inverse_mass(self.handle, bp, R, dp, ptrs[0], space), "rsb_apply_inverse_mass")
+        return res["X"]
+
+    def frame_delassus(self, frames, angular=False, joint_diag=None, G=True, JMinv=False, out=None):
+        """The operational-space matrices of every env at the resident configuration -> {"G": [N, kF, kF] = J (M + D)^-1 J^T, "JMinv": [N, kF, nv]
+        = J (M + D)^-1}, the outputs asked for only.  J stacks the rows of frame_jacobians: k = 3 rows per frame (lin), or with angular=True k = 6
+        (lin, then rot).  G equals its transpose bit for bit and may be singular; Lambda = G^-1 (a damped Cholesky, say) is the caller's.
+        frames: at most 16, as in frame_kinematics; joint_diag as in apply_inverse_mass.  out: see _frame_outputs."""
+        arr, n = self._frames(frames)
+        k = (6 if angular else 3) * n
+        shapes = {"G": (self.N, k, k), "JMinv": (self.N, k, self.nv)}
+        space, ptrs, out = self._frame_outputs(("G", "JMinv"), dict(G=G, JMinv=JMinv), shapes, out, "frame_delassus")
+        dp, dkeep = self._joint_diag("frame_delassus", joint_diag)
+        check(self.L.rsb_get_frame_delassus(self.handle, arr, n, _capi.RSB_DELASSUS_ANGULAR if angular else 0, dp, *ptrs, space), "rsb_get_frame_delassus")
+        return out
+
     # -- terrain: heights, height scans and ray tests of every env in one call (rsb_terrain_query.hip) -------------------
     def _terrain_io(self, what, inputs, out_shapes, out):
         """inputs {name: (value, shape)}, out_shapes {name: shape}, out {name: array / tensor or None} -> (space, input pointers, output pointers,

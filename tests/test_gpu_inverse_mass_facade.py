@@ -1,0 +1,17 @@
+"""BatchedWorld::applyInverseMass / getFrameDelassus through the C++ facade on the GPU (tests/cpp/inverse_mass_facade_test.cpp): the batched members on
+host buffers against the C-ABI they wrap, bit for bit - on the facade's own world and on a second world that received the same rows through
+rsb_set_state, so the rows staged through the per-env views must have been uploaded first - in place, null outputs skipped, G symmetric, M X = B."""
+import subprocess
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+
+def test_inverse_mass_facade_against_the_c_abi(built_lib):
+    from test_inverse_mass_host import BIN, URDF, compile_inverse_mass_facade
+    compile_inverse_mass_facade()
+    r = subprocess.run([BIN, URDF], capture_output=True, text=True, timeout=300)
+    print(r.stdout)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "inverse_mass_facade_test OK" in r.stdout
