@@ -30,7 +30,11 @@
           int lca = 0;
           bool same = true;
           RSB_UNROLL for (int l = 0; l < ML; ++l) { same = same && (ai[l] == aj[l]); lca += same ? 1 : 0; }
+#if RSB_FLAT_SETUP_HEAD
+          constexpr int CWC = 6 + RSB_SPEC_DEPTH - 1;   // (the tree's own depth: an entry past it exists in no column, and cost nine FMAs and six selects on zeros)
+#else
           constexpr int CWC = 6 + ML;          // compile-time bound of the compact column width
+#endif
           float wi[3][CWC], wj[3][CWC];
           const float* Wi = WC + (3 * i) * cw;
           const float* Wj = WC + (3 * j) * cw;

@@ -31,6 +31,46 @@
         RSB_UNROLL for (int q2 = 0; q2 < 9; ++q2) Gii[q2] = 0.f;
         RSB_UNROLL for (int q2 = 0; q2 < 12; ++q2) Ginv[q2] = 0.f;
         v[0] = v[1] = v[2] = 0.f;
+#if RSB_FLAT_CLASS
+        asm volatile("; rsb setup begin");     // (tests/test_flat_setup_host.py counts between the comment lines)
+#endif
+#if RSB_FLAT_SETUP_HEAD
+        // flat set-up (step_spec.h): two batches of LDS reads and no exec-mask region.  Batch A is everything the lane index alone addresses - the own block, its
+        // inverse, the own velocity, floats 4-11 of the contact record (body AND collision id), the five coupling blocks of the exchange's straight part - read by
+        // every lane at the clamped slot a lane without a contact always used for its coupling rows.  Such a lane holds whatever that slot holds; nothing it computes
+        // from it is ever used (every result that leaves a lane is selected by isc, mine, need or lost; its impulse stays the literal zero).
+        static_assert(GROWS && !TRI, "flat set-up: the row-block layout of the quadruped classes");
+        const int sq = min(s, KMAX - 1);
+        float fq0[5][4], fq1[5][4], fq2[5], fc4[4], fc8[4];
+        {
+          float D[3][3];
+          gblk_load(Gmine + kGBlock * sq, D);
+          ldv<3>(GINV + 12 * sq, Ginv);
+          v[0] = CV[3 * sq]; v[1] = CV[3 * sq + 1]; v[2] = CV[3 * sq + 2];
+          ld4(CON + sq * kConSlot + 4, fc4); ld4(CON + sq * kConSlot + 8, fc8);
+          RSB_UNROLL for (int k = 0; k < 5; ++k) { ld4(Gmine + kGBlock * k, fq0[k]); ld4(Gmine + kGBlock * k + 4, fq1[k]); fq2[k] = Gmine[kGBlock * k + 8]; }
+          RSB_UNROLL for (int rr = 0; rr < 3; ++rr) RSB_UNROLL for (int cc = 0; cc < 3; ++cc) Gii[3 * rr + cc] = D[rr][cc];
+        }
+        // Batch B is what the record addresses, behind ONE wait: the body's level and ancestor row, the primitive's friction coefficient and its warm row.  A lane
+        // without a contact asks for body 0; a joint-limit row, a self-collision entry and such a lane for a primitive of the table (the index clamped) - what they
+        // get is discarded below by selects on the RESULTS (a stale warm row may hold anything: never a product with a zero).
+        const int kb = isc ? __float_as_int(fc4[3]) : 0;
+        const int mycol = isc ? __float_as_int(fc8[3]) : 0;
+        const int fci = min(mycol & 0xffff, ncol - 1);
+        const int fpl = PARLV[kb];
+        int fanc[4] = {0, -1, -1, -1};      // the body's ancestor row: kept for the impulse scatter that ends the solve
+#if RSB_SPEC_DEPTH == 4
+        { const int4 r4 = *reinterpret_cast<const int4*>(ANC + kb * 4); fanc[1] = r4.y; fanc[2] = r4.z; fanc[3] = r4.w; }
+#else
+        RSB_UNROLL for (int lv = 1; lv < RSB_SPEC_DEPTH; ++lv) fanc[lv] = ANC[kb * RSB_SPEC_DEPTH + lv];
+#endif
+        const float fmu = COLT[kColSlot * fci + 5];
+        float fwr[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (has_warm) { RSB_UNROLL for (int i = 0; i < 6; ++i) fwr[i] = WARM[6 * fci + i]; }
+        __builtin_amdgcn_sched_barrier(0);      // (the whole batch is issued before its first result is waited for: left alone the scheduler puts the level test, and its wait, in front of the other reads)
+        int gidc = isc ? (((fpl >> 8) >= 1) ? fanc[1] : 0) : -1 - s;            // limb of the own contact (non-contact lanes: an id nobody shares)
+        float fsmu = 0.f;
+#else
         int gidc = -1 - s;            // limb of the own contact (non-contact lanes: an id nobody shares)
         if (isc) {
           if constexpr (GROWS) {   // the own block of the own row
@@ -49,11 +89,17 @@
           const int kb = __float_as_int(CON[s * kConSlot + 7]);
           gidc = ((PARLV[kb] >> 8) >= 1) ? ANC[kb * depth + 1] : 0;
         }
+#endif
         // the solver's parameters, read here so that they occupy SGPRs during the solve only
         RSB_ARGS(ag);
         // the own contact's friction coefficient: that of its collision primitive against the terrain (material pairs)
+#if !RSB_FLAT_SETUP_HEAD
         const int mycol = isc ? __float_as_int(CON[s * kConSlot + 11]) : 0;
+#endif
         if (__any(nselfc > 0)) {   // rare
+#if RSB_FLAT_SETUP_HEAD
+          fsmu = SELFT[4 * sq];      // (a self-collision's material pair: read by every lane behind the wave-uniform test, taken below by its first entry)
+#endif
           // a self-collision couples its two limbs strongly: their groups are merged (oracle: the same relabelling, in contact
           // order); the inert second entries keep ids of their own
           const bool prim = isc && (mycol & kSelfA) != 0;
@@ -67,9 +113,15 @@
             if (jp && lo != hi) { gidc = (gidc == hi) ? lo : gidc; gidb = (gidb == hi) ? lo : gidb; }
           }
         }
+#if RSB_FLAT_SETUP_HEAD
+        float mu = (isc && mycol < ncol) ? fmu : RSB_DIM_F32(MU, ag.mu);
+        if constexpr (HM2) mu = (isc && (mycol & kExtra)) ? fmu : mu;      // (the same table entry: mycol & 0xffff is mycol itself below ncol)
+        mu = (mycol & kSelfA) ? fsmu : mu;    // material pair of the two primitives (an env with such an entry has nselfc > 0)
+#else
         float mu = (isc && mycol < ncol) ? COLT[kColSlot * mycol + 5] : RSB_DIM_F32(MU, ag.mu);
         if constexpr (HM2) { if (isc && (mycol & kExtra)) mu = COLT[kColSlot * (mycol & 0xffff) + 5]; }
         if (mycol & kSelfA) mu = SELFT[4 * s];    // material pair of the two primitives
+#endif
         const float mu2 = mu * mu;
         const float alpha_init = RSB_DIM_F32(ALPHA_INIT, ag.alpha_init), alpha_min = RSB_DIM_F32(ALPHA_MIN, ag.alpha_min), alpha_decay = RSB_DIM_F32(ALPHA_DECAY, ag.alpha_decay);
         const float threshold = RSB_DIM_F32(THRESHOLD, ag.threshold), stall_factor = RSB_DIM_F32(STALL_FACTOR, ag.stall_factor);
@@ -185,6 +237,13 @@
         if constexpr (PK && !TRI) {
           // (the exchange reads blocks 0-4 whatever the count; 5-7 only behind its `ncw > 5` tests: the usual wave - four or five contacts per env - does not load them)
           RSB_UNROLL for (int k = 0; k < NPK; ++k) {
+#if RSB_FLAT_SETUP_HEAD
+            static_assert(NPK >= 5, "flat set-up: batch A reads the five blocks of the exchange's straight part");
+            if (k < 5) {      // (read with batch A)
+              gp[k][0] = float2v{fq0[k][0], fq0[k][1]}; gp[k][1] = float2v{fq0[k][2], fq0[k][3]}; gp[k][2] = float2v{fq1[k][0], fq1[k][1]};
+              gr[k][0] = fq1[k][2]; gr[k][1] = fq1[k][3]; gr[k][2] = fq2[k < 5 ? k : 0];
+            } else
+#endif
             if (k < 5 || ncw > 5) {
               if constexpr (GROWS) {   // the block is stored as the pairs and the third row: two 16-byte reads and one scalar
                 float q0[4], q1[4];
@@ -268,6 +327,19 @@
         // warm start (oracle: lam_warm): the impulse and friction direction this collision primitive had at the end of
         // the previous integrate(); the table is then cleared, contacts alive at the end of this solve re-enter it
         if (has_warm) {
+#if RSB_FLAT_SETUP_HEAD
+          {
+            const bool wok = isc && mycol < ncol;   // joint-limit rows (ids >= ncol) start cold: the row read with batch B is taken or dropped whole
+            lam[0] = wok ? fwr[0] : 0.f; lam[1] = wok ? fwr[1] : 0.f; lam[2] = wok ? fwr[2] : 0.f;
+            sdx = wok ? fwr[3] : 0.f; sdy = wok ? fwr[4] : 0.f; sdst = (wok && fwr[5] != 0.f) ? 3 : 0;
+          }
+          // the table is cleared by straight stores: a compile-time trip count, the last trip's index clamped to the table's last float (several lanes then store
+          // the same zero to it) - no region, no skip branch
+          {
+            constexpr int kNw = 6 * RSB_SPEC_NCOL, kTrips = (kNw + LPE - 1) / LPE;
+            RSB_UNROLL for (int t = 0; t < kTrips; ++t) WARM[(LPE * (t + 1) <= kNw) ? s + LPE * t : min(s + LPE * t, kNw - 1)] = 0.f;
+          }
+#else
           if (isc) {
             if (mycol < ncol) {   // joint-limit rows (ids >= ncol) start cold
               const float* wr = WARM + 6 * mycol;
@@ -276,13 +348,21 @@
             }
           }
           for (int i = s; i < nwarm; i += LPE) WARM[i] = 0.f;
+#endif
+#if RSB_FLAT_SETUP_HEAD
+          if (__any(isc & ((lam[0] != 0.f) | (lam[1] != 0.f) | (lam[2] != 0.f)))) {      // (no short circuit: the compiler builds a region for one)
+#else
           if (__any(isc && (lam[0] != 0.f || lam[1] != 0.f || lam[2] != 0.f))) {
+#endif
             // v = c + G lam(0): one exchange of the inherited impulses (v carries the own impulse as well)
             float unused = 0.f;
             exchange(lam, unused);
           }
         }
         if (PROF && pfine) { t_prev = t_gs0; lap(t_setup); }
+#if RSB_FLAT_CLASS
+        asm volatile("; rsb setup end");
+#endif
 
         // global search of contact j's direction by its 16-lane row (coefficients broadcast from lane j)
         auto search_row = [&](int j, const SlipCoef& kc, bool take) {
@@ -556,14 +636,23 @@
 #if RSB_PK_CLASS
         asm volatile("; rsb sweep end");
 #endif
+#if RSB_FLAT_CLASS
+        asm volatile("; rsb solver end begin");     // (tests/test_flat_setup_host.py counts between the comment lines)
+#endif
         if (PROF && pfine) tz0 = t_prev;
+#if RSB_FLAT_SETUP_END
+        flag |= converged ? 0 : 4;      // (selects: the calmest iterate of an env that did not converge)
+        lam[0] = converged ? lam[0] : lam_best[0]; lam[1] = converged ? lam[1] : lam_best[1]; lam[2] = converged ? lam[2] : lam_best[2];
+#else
         if (!converged) { flag |= 4; lam[0] = lam_best[0]; lam[1] = lam_best[1]; lam[2] = lam_best[2]; }
+#endif
         if (__any(nselfc > 0)) {   // the second entry of a self-collision carries the first one's impulse (in its opposite frame)
           RSB_UNROLL for (int rr = 0; rr < 3; ++rr) {
             const float up = __shfl_up(lam[rr], 1);
             lam[rr] = (mycol & kSelfB) ? up : lam[rr];
           }
         }
+#if !RSB_FLAT_SETUP_END
         if (isc) {
           LAM[3 * s] = lam[0]; LAM[3 * s + 1] = lam[1]; LAM[3 * s + 2] = lam[2];
           if (has_warm && mycol < ncol) {
@@ -572,6 +661,7 @@
             wr[3] = sdst ? sdx : 0.f; wr[4] = sdst ? sdy : 0.f; wr[5] = sdst ? 1.f : 0.f;
           }
         }
+#endif
         // W^T lam: the base entries are summed over the contact lanes by a DPP row reduction (contact lanes sit in the env's
         // first row; wider envs copy the sums to their other rows); the joint entries are scattered into WB of the
         // support chain with LDS float atomics (lanes of one instruction are served in lane order: reproducible)
@@ -580,16 +670,60 @@
           const float* W0 = WC + 3 * sc2 * cw;
           float z0[8], z1[8], z2[8];
           ld4(W0, z0); ld4(W0 + 4, z0 + 4); ld4(W0 + cw, z1); ld4(W0 + cw + 4, z1 + 4); ld4(W0 + 2 * cw, z2); ld4(W0 + 2 * cw + 4, z2 + 4);
+#if RSB_FLAT_SETUP_END
+          // flat end (step_spec.h): ONE batch of reads in front of the row sums - the column's rows, its entries of level 3 and up, and the ancestor row where the
+          // set-up did not leave it in registers - read by every lane (a lane without a contact reads contact 0's column and body 0's row, as it reads that column's
+          // rows above); the contact lanes' ONE region then holds nothing but the stores and the three atomics.
+          float zt[3][RSB_SPEC_DEPTH > 3 ? RSB_SPEC_DEPTH - 3 : 1];
+          RSB_UNROLL for (int lv = 3; lv < RSB_SPEC_DEPTH; ++lv) { zt[0][lv - 3] = W0[5 + lv]; zt[1][lv - 3] = W0[cw + 5 + lv]; zt[2][lv - 3] = W0[2 * cw + 5 + lv]; }
+          // (pinned: left alone the compiler sinks the reads whose only use is a contact lane's into regions of their own, each with its wait)
+          RSB_UNROLL for (int i = 0; i < 8; ++i) asm volatile("" : "+v"(z0[i]), "+v"(z1[i]), "+v"(z2[i]));
+#if !RSB_FLAT_SETUP_HEAD
+          int fanc[4] = {0, -1, -1, -1};
+          {
+            const int bi = isc ? __float_as_int(CON[sc2 * kConSlot + 7]) : 0;
+#if RSB_SPEC_DEPTH == 4
+            const int4 r4 = *reinterpret_cast<const int4*>(ANC + bi * 4); fanc[1] = r4.y; fanc[2] = r4.z; fanc[3] = r4.w;
+#else
+            RSB_UNROLL for (int lv = 1; lv < RSB_SPEC_DEPTH; ++lv) fanc[lv] = ANC[bi * RSB_SPEC_DEPTH + lv];
+#endif
+          }
+#endif
+#endif
           const float l0 = isc ? lam[0] : 0.f, l1 = isc ? lam[1] : 0.f, l2 = isc ? lam[2] : 0.f;
           // (select, not a product with a zero impulse: a lane without a contact reads column memory nobody wrote)
           RSB_UNROLL for (int i = 0; i < 6; ++i) wlam[i] = row_sum_f32(isc ? z0[i] * l0 + z1[i] * l1 + z2[i] * l2 : 0.f);
           if constexpr (LPE > 16) {   // body lanes beyond the env's first row need the sum too (level-1 bodies start from the base's delta-velocity)
             RSB_UNROLL for (int i = 0; i < 6; ++i) wlam[i] = __shfl(wlam[i], (lane & ~(LPE - 1)) | (lane & 15));
           }
-#if RSB_FLAT_CLASS
+#if RSB_FLAT_CLASS && !RSB_FLAT_SETUP_END
           asm volatile("; rsb scatter begin");     // (tests/test_flat_contact_host.py counts between the comment lines)
 #endif
-#if RSB_FLAT_SCATTER
+#if RSB_FLAT_SETUP_END
+          if (isc) {
+            // (the flat scatter below, on the reads of the batch above; the impulse and the warm record are stored in the same region)
+            LAM[3 * s] = lam[0]; LAM[3 * s + 1] = lam[1]; LAM[3 * s + 2] = lam[2];
+            if (has_warm && mycol < ncol) {
+              float* wr = WARM + 6 * mycol;
+              wr[0] = lam[0]; wr[1] = lam[1]; wr[2] = lam[2];
+              wr[3] = sdst ? sdx : 0.f; wr[4] = sdst ? sdy : 0.f; wr[5] = sdst ? 1.f : 0.f;
+            }
+            asm volatile("; rsb scatter begin");     // (the scatter proper, inside the one region: tests/test_flat_contact_host.py counts between the comment lines)
+            float* sink = WC + 3 * s * cw + kFlatSink;
+            float wl[4] = {0.f, 0.f, 0.f, 0.f};
+            RSB_UNROLL for (int lv = 1; lv < RSB_SPEC_DEPTH; ++lv) {
+              float w0, w1, w2;
+              if (lv < 3) { w0 = z0[5 + lv]; w1 = z1[5 + lv]; w2 = z2[5 + lv]; }
+              else { w0 = zt[0][lv < 3 ? 0 : lv - 3]; w1 = zt[1][lv < 3 ? 0 : lv - 3]; w2 = zt[2][lv < 3 ? 0 : lv - 3]; }
+              wl[lv] = w0 * lam[0] + w1 * lam[1] + w2 * lam[2];      // (a contact lane's l0..l2 ARE its impulse: read from there, the selects above stay out of this region)
+            }
+            RSB_UNROLL for (int lv = 1; lv < RSB_SPEC_DEPTH; ++lv) {
+              float* dst = (fanc[lv] >= 0) ? &WB[fanc[lv] + 5] : sink;
+              atomicAdd(dst, wl[lv]);
+            }
+            asm volatile("; rsb scatter end");
+          }
+#elif RSB_FLAT_SCATTER
           if (isc) {
             // flat form (step_spec.h): ONE region, the contact lanes'; inside it the atomics are issued straight, in their level order, behind every read.  A level
             // the body has no ancestor at adds onto the sink of the lane's own column - another address, so the lanes of an instruction that do add onto WB are
@@ -635,10 +769,13 @@
             }
           }
 #endif
-#if RSB_FLAT_CLASS
+#if RSB_FLAT_CLASS && !RSB_FLAT_SETUP_END
           asm volatile("; rsb scatter end");
 #endif
         }
+#if RSB_FLAT_CLASS
+        asm volatile("; rsb solver end end");
+#endif
       }
       __syncthreads();
       if (PROF && pfine) t_end += clock64() - tz0;

@@ -176,6 +176,40 @@ static_assert(kFlatSink >= 6 + RSB_SPEC_DEPTH - 1 && kFlatSink < kFlatCw, "flat 
 }  // namespace rsbk
 #endif
 
+// Flat set-up and end of the contact solve (step_phase_solver.inc), in the same code objects (row-block Delassus layout, energy slip rule).  A launch of these classes is
+// one wave per SIMD: nothing hides an LDS round trip, and the set-up was a CHAIN of them - the contact record's body, that body's level, its ancestor; the record's
+// collision id (a second read, in its own exec-mask region), the primitive's friction coefficient, its warm row - with the coupling blocks, which only the lane index
+// addresses, issued behind all of it.  The end re-read the record's body and its ancestor row behind the row sums.
+//   RSB_FLAT_SETUP_HEAD  two batches and no region.  Batch A: everything the lane index addresses (own block, inverse, velocity, floats 4-11 of the contact record as
+//                        two 16-byte reads, the five coupling blocks), read by every lane at the clamped slot.  Batch B, behind one wait: PARLV and the ancestor row of
+//                        the record's body, the friction coefficient and the warm row at a clamped primitive.  Selects then take or drop the RESULTS (a dropped warm
+//                        row is never multiplied by a zero: it may hold anything).  The self-collision's relabelling and its SELFT read stay behind their one
+//                        wave-uniform test.  The warm table is cleared by straight stores (a compile-time trip count, the last index clamped).  The ancestor row stays
+//                        in registers for the end.  With it the Delassus loop's column bound is the tree's depth, not the class's level capacity.
+//   RSB_FLAT_SETUP_END   (beside RSB_FLAT_SCATTER) one batch of reads in front of the row sums - the column rows with their level-3 entries, and the ancestor row
+//                        where the set-up did not keep it - and ONE region of the contact lanes with the impulse stores, the warm record and the three atomics.
+// -DRSB_X_NO_FLAT_SETUP compiles the code as it was, -DRSB_X_NO_FLAT_SETUP_HEAD / -DRSB_X_NO_FLAT_SETUP_END one part of it: same results bit for bit
+// (tests/test_gpu_flat_setup.py).  The code objects of RSB_FLAT_CLASS carry the comment lines `; rsb setup begin/end` and `; rsb solver end begin/end`, switch or not
+// (tests/test_flat_setup_host.py counts between them).
+// The fixed-base classes (| 1) do not take the form: which product of the scatter's three-term sums the compiler leaves unfused is its choice per code object, and in the
+// fixed-base class of a two-level tree the end's form came out one rounding away from the code it replaces (15 entries of u after four steps of
+// tests/test_gpu_solver_handover.py's model; the quadruped's classes keep every bit: tests/test_gpu_flat_setup.py).  A fixed-base world is no quadruped.
+#if RSB_FLAT_CLASS && !((RSB_I_CL) & (32 | 1)) && !defined(RSB_X_G_SQUARE) && !defined(RSB_X_NO_FLAT_SETUP)
+#define RSB_FLAT_SETUP 1
+#else
+#define RSB_FLAT_SETUP 0
+#endif
+#if RSB_FLAT_SETUP && !defined(RSB_X_NO_FLAT_SETUP_HEAD)
+#define RSB_FLAT_SETUP_HEAD 1
+#else
+#define RSB_FLAT_SETUP_HEAD 0
+#endif
+#if RSB_FLAT_SETUP && RSB_FLAT_SCATTER && !defined(RSB_X_NO_FLAT_SETUP_END)
+#define RSB_FLAT_SETUP_END 1
+#else
+#define RSB_FLAT_SETUP_END 0
+#endif
+
 // Packed fp32 form of the contact solve's arithmetic, in the specialised code objects of the quadruped classes (16 lanes per env, eight contact slots or fewer, the
 // energy slip rule: lock-step, pipelined, resident and closed-loop).  Such a launch is one wave per SIMD, and a lone wave pays ~4 cycles for every VALU instruction
 // it issues whatever the instruction does (profiles/r02_ubench_lone_wave_latency.txt), so two fp32 operations that share an operand pattern are written as ONE
