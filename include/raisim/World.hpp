@@ -338,6 +338,26 @@ class BatchedWorld {
     RSB_CHECK(rsb_forward_dynamics(world_, tau, frames.empty() ? nullptr : frames.data(), (int)frames.size(), force, torque, contacts ? RSB_DYN_CONTACTS : 0, udot,
                                    RSB_HOST));
   }
+  /// The exact derivatives of inverseDynamics(udot, loads) for ALL envs in one call, on the device, at the resident state (staged view rows are
+  /// uploaded first): dTauDq, dTauDv, dTauDudot [N,dof(),dof()], entry [e][i][j] = d tau_i / d x_j, d gv_j, d udot_j (the last is the mass matrix);
+  /// any may be null, not all.  x is the tangent coordinate of gc in gv's order: the base origin along the world axes, the base rotated about the
+  /// WORLD axes (the quaternion multiplied on the left), the joint coordinates.  gv, udot, gravity and the loads' world force / torque are held
+  /// fixed; a load's point moves with its body.  Host buffers; no contacts; the world is left as it was.
+  void inverseDynamicsDerivatives(const float* udot, const std::vector<rsb_frame>& frames, const float* force, const float* torque, float* dTauDq, float* dTauDv,
+                                  float* dTauDudot) {
+    std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
+    RSB_CHECK(rsb_inverse_dynamics_derivatives(world_, udot, frames.empty() ? nullptr : frames.data(), (int)frames.size(), force, torque, 0, dTauDq, dTauDv, dTauDudot,
+                                               RSB_HOST));
+  }
+  /// The exact derivatives of forwardDynamics(tau, loads) for ALL envs in one call: udot [N,dof()] the forward dynamics itself, dUdotDq = -M^-1 dTauDq
+  /// at that udot, dUdotDv = -M^-1 dTauDv, dUdotDtau = M^-1, each [N,dof(),dof()]; any may be null, not all.  The conventions of
+  /// inverseDynamicsDerivatives.  With S the selection of the actuated rows: A = [[0, I], [dUdotDq, dUdotDv]], B = [[0], [dUdotDtau S^T]].
+  void forwardDynamicsDerivatives(const float* tau, const std::vector<rsb_frame>& frames, const float* force, const float* torque, float* udot, float* dUdotDq,
+                                  float* dUdotDv, float* dUdotDtau) {
+    std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
+    RSB_CHECK(rsb_forward_dynamics_derivatives(world_, tau, frames.empty() ? nullptr : frames.data(), (int)frames.size(), force, torque, 0, udot, dUdotDq, dUdotDv,
+                                               dUdotDtau, RSB_HOST));
+  }
   /// X [N,R,dof()] = (M(q) + diag(jointDiag))^-1 B for ALL envs in one call, on the device, at the resident configuration, without the dense
   /// getInverseMassMatrix(): one articulated-body factorisation per env, two tree passes per column.  Host buffers; X may be B.  jointDiag [dof()]
   /// (null: zeros): non-negative, zero on a floating base's six entries; dt (kd + dt kp) gives the effective mass the contact problem sees.

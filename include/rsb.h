@@ -38,6 +38,9 @@
  *   rsb_inverse_dynamics / rsb_forward_dynamics
  *                                       <- ArticulatedSystem::setComputeInverseDynamics / getForceAtJointInWorldFrame /
  *                                          getTorqueAtJointInWorldFrame, and the plain equations of motion, for all envs in one call
+ *   rsb_inverse_dynamics_derivatives / rsb_forward_dynamics_derivatives
+ *                                       <- (new) the analytic derivatives of the two with respect to configuration, velocity and
+ *                                          acceleration / force, for all envs in one call
  *   rsb_apply_inverse_mass / rsb_get_frame_delassus
  *                                       <- (new) M^-1 B and the operational-space matrices J M^-1, J M^-1 J^T at chosen frames, for all
  *                                          envs in one call, without the dense getInverseMassMatrix()
@@ -409,6 +412,48 @@ int rsb_forward_dynamics(rsb_world* w,
                          const float* tau,             /* [N,nv] in `space`; NULL = the resident feed-forward rows       */
                          const rsb_frame* frames, int n_frames, const float* force, const float* torque, int flags,
                          float* udot,                  /* [N,nv]                                                         */
+                         int space);
+
+/* The slopes of the two queries above: exact (analytic, forward-mode) derivatives of inverse and forward dynamics at the resident state, for ALL envs
+ * in one call.  The same rules: HIP kernels on the world's stream (a pipelined world is joined first); the RSB_DEVICE forms do not synchronise, the
+ * RSB_HOST forms stage through the same device buffer (which also holds the forward form's intermediates: it grows on first use).  Both read the
+ * resident gc / gv (the base quaternion normalised first) and the world's gravity.  Neither changes a bit of the world.  An error touches no output.
+ * No atomics, every sum in a fixed order: env e's results depend on env e's rows alone - the same bits for any N and any subset of outputs.
+ *
+ * Every matrix is [N,nv,nv], entry [e,i,j] the derivative of row i with respect to coordinate j.
+ * x_j, the coordinate of dtau_dq / dudot_dq, is the TANGENT coordinate of gc that matches gv's order, so that d gc / dt corresponds to gv exactly:
+ *     j < 3         the base origin moves by eps along world axis j;
+ *     3 <= j < 6    the base rotates by eps about WORLD axis j-3:  R_0 <- exp(eps [e]x) R_0  (the quaternion is multiplied on the LEFT);
+ *     j >= 6        joint coordinate gc[j-6+7] grows by eps.
+ * While x varies the components of gv, udot, tau and gravity are held fixed as arrays.  A load's world force and torque are held fixed; its point of
+ * application stays fixed ON ITS BODY, so it moves with x.  dtau_dv / dudot_dv: with respect to the components of gv.  The armature contributes to
+ * dtau_dudot only.  Columns j < 3 of dtau_dq are exact zeros (translation invariance).
+ *
+ * rsb_inverse_dynamics_derivatives:  tau = rsb_inverse_dynamics(udot, loads);  dtau_dudot = M(q) (armature on the diagonal).
+ * rsb_forward_dynamics_derivatives:  the implicit-function derivatives at udot* = rsb_forward_dynamics(tau, loads), which `udot` receives:
+ *     dudot_dq = -M^-1 dtau_dq |udot*        dudot_dv = -M^-1 dtau_dv        dudot_dtau = M^-1
+ *   M^-1 is applied by the factorisation of rsb_apply_inverse_mass (once per env in double, the columns in float); dudot_dtau[e,i,j] carries the bits
+ *   of rsb_apply_inverse_mass(identity)[e,j,i].
+ * flags must be 0: there are no derivatives with RSB_DYN_CONTACTS.
+ * Fixed-base models: the six base COLUMNS of every matrix are zero.  The base ROWS of the inverse-dynamics matrices are the derivatives of the holding
+ * wrench tau[0:6]; the base rows of the forward-dynamics matrices (and of udot) are zero.  No bit of the base entries of gv, udot or tau matters.
+ * RSB_E_INVALID, with a message naming the function: the argument errors of rsb_inverse_dynamics, and non-zero flags. */
+int rsb_inverse_dynamics_derivatives(rsb_world* w,
+                         const float* udot,            /* [N,nv] in `space`; NULL = zeros                                */
+                         const rsb_frame* frames, int n_frames,   /* external loads as in rsb_inverse_dynamics           */
+                         const float* force, const float* torque, /* [N,F,3] in `space`; either may be NULL              */
+                         int flags,                    /* must be 0                                                      */
+                         float* dtau_dq,               /* [N,nv,nv]  d tau_i / d x_j                                     */
+                         float* dtau_dv,               /* [N,nv,nv]  d tau_i / d gv_j                                    */
+                         float* dtau_dudot,            /* [N,nv,nv]  = M(q); any output may be NULL, not all             */
+                         int space);
+int rsb_forward_dynamics_derivatives(rsb_world* w,
+                         const float* tau,             /* [N,nv] in `space`; NULL = the resident feed-forward rows       */
+                         const rsb_frame* frames, int n_frames, const float* force, const float* torque, int flags,
+                         float* udot,                  /* [N,nv]  the forward dynamics itself                            */
+                         float* dudot_dq,              /* [N,nv,nv]                                                      */
+                         float* dudot_dv,              /* [N,nv,nv]                                                      */
+                         float* dudot_dtau,            /* [N,nv,nv]  = M^-1; any output may be NULL, not all             */
                          int space);
 
 /* M(q)^-1 applied to what the caller chooses, for ALL envs in one call, without forming M: the articulated-body factorisation of rsb_forward_dynamics

@@ -215,6 +215,8 @@ PROTOTYPES = {
     "rsb_get_centroidal_momentum_matrix": (_I, [_VP, _FP, _I]),
     "rsb_inverse_dynamics": (_I, [_VP, _FP, C.POINTER(Frame), _I, _FP, _FP, _I, _FP, _FP, _FP, _I]),
     "rsb_forward_dynamics": (_I, [_VP, _FP, C.POINTER(Frame), _I, _FP, _FP, _I, _FP, _I]),
+    "rsb_inverse_dynamics_derivatives": (_I, [_VP, _FP, C.POINTER(Frame), _I, _FP, _FP, _I, _FP, _FP, _FP, _I]),
+    "rsb_forward_dynamics_derivatives": (_I, [_VP, _FP, C.POINTER(Frame), _I, _FP, _FP, _I, _FP, _FP, _FP, _FP, _I]),
     "rsb_apply_inverse_mass": (_I, [_VP, _FP, _I, _FP, _FP, _I]),
     "rsb_get_frame_delassus": (_I, [_VP, C.POINTER(Frame), _I, _I, _FP, _FP, _FP, _I]),
     "rsb_get_terrain_height": (_I, [_VP, _FP, _I, _FP, _FP, _I]),

@@ -218,21 +218,25 @@ inline unsigned env_blocks(const rsb_world* w) { return blocks_for((size_t)w->N,
 // the launch, end().  RSB_DEVICE: every slot is the caller's own pointer and begin() / end() do nothing.  RSB_HOST: begin() sizes the world's
 // staging buffer for exactly what is not NULL, gives each such buffer its slice in declaration order and enqueues the inputs' copies on the world's
 // stream; end() brings the outputs back in declaration order through copy_out, which waits for the stream (the caller may reuse its host buffers on
-// return) and reports a fault once - or, with no output, waits for the stream itself.
+// return) and reports a fault once - or, with no output, waits for the stream itself.  scratch() asks for device floats at the head of the same
+// buffer in either space: what a query made of several launches hands from one to the next.
 class Staged {
  public:
   Staged(rsb_world* w, int space) : w_(w), host_(space == RSB_HOST) {}
   void in(const float*& dev, const float* host, size_t floats) { dev = host; add({host, floats * sizeof(float), &dev, nullptr, nullptr}); }
   void in(const uint8_t*& dev, const uint8_t* host, size_t bytes) { dev = host; add({host, bytes, nullptr, &dev, nullptr}); }
   void out(float*& dev, float* host, size_t floats) { dev = host; add({host, floats * sizeof(float), nullptr, nullptr, &dev}); }
+  void scratch(float*& dev, size_t floats) { dev = nullptr; scratch_slot_ = &dev; scratch_ = floats; }
   int begin() {
     if (n_ > kMax) return invalid("Staged", "more than " + std::to_string(kMax) + " buffers declared");
-    if (!host_) return RSB_OK;
-    size_t total = 0;
-    for (int k = 0; k < n_; ++k) total += floats(items_[k]);
+    if (!host_ && !scratch_) return RSB_OK;
+    size_t total = scratch_;
+    for (int k = 0; host_ && k < n_; ++k) total += floats(items_[k]);
     const int st = staging(w_, total); if (st != RSB_OK) return st;
-    hipStream_t s = stream_of(w_);
     float* b = w_->d_frames_io;
+    if (scratch_) { *scratch_slot_ = b; b += scratch_; }
+    if (!host_) return RSB_OK;
+    hipStream_t s = stream_of(w_);
     for (int k = 0; k < n_; ++k) {
       const Item& it = items_[k];
       if (!it.out) HIP_TRY(hipMemcpyAsync(b, it.host, it.bytes, hipMemcpyHostToDevice, s));
@@ -265,6 +269,8 @@ class Staged {
   static constexpr int kMax = 8;
   Item items_[kMax];
   int n_ = 0;
+  float** scratch_slot_ = nullptr;
+  size_t scratch_ = 0;
 };
 
 }  // namespace

@@ -341,8 +341,10 @@ __global__ __launch_bounds__(kThreads) void aba_kernel(const DevModel* __restric
   for (int e = threadIdx.x; e < here * nv; e += kThreads) out[e] = outl[e];
 }
 
+}  // namespace
+
 // the argument checks both entry points share (after check_world); RSB_OK, or RSB_E_INVALID with a message
-int check_loads(const rsb_world* w, const char* who, const rsb_frame* frames, int n_frames, const float* force, const float* torque, int flags) {
+int check_dynamics_loads(const rsb_world* w, const char* who, const rsb_frame* frames, int n_frames, const float* force, const float* torque, int flags) {
   if (n_frames < 0 || n_frames > RSB_MAX_FRAMES) return invalid(who, "n_frames must be 0.." + std::to_string(RSB_MAX_FRAMES));
   if (n_frames > 0) {
     if (!frames) return invalid(who, "frames is NULL with n_frames > 0");
@@ -353,6 +355,8 @@ int check_loads(const rsb_world* w, const char* who, const rsb_frame* frames, in
   return RSB_OK;
 }
 
+namespace {
+
 // what the launch hands the kernels: the staged loads (either may be null) and, with RSB_DYN_CONTACTS, the resident contact list
 Loads loads_of(const rsb_world* w, const float* force, const float* torque, int n_frames, int flags) {
   const bool contacts = (flags & RSB_DYN_CONTACTS) != 0;
@@ -360,6 +364,16 @@ Loads loads_of(const rsb_world* w, const float* force, const float* torque, int 
 }
 
 }  // namespace
+
+int launch_forward_dynamics(rsb_world* w, hipStream_t s, const float* tau, const rsb_frame* frames, int n_frames, const float* force, const float* torque, int flags,
+                            float* udot) {
+  hipLaunchKernelGGL(aba_kernel, dim3(env_blocks(w)), dim3(kThreads), 0, s, (const DevModel*)w->d_model, (const float*)w->d_gc, (const float*)w->d_gv,
+                     tau ? tau : (const float*)w->d_tff, n_frames ? frame_list(frames, n_frames) : FrameList{}, loads_of(w, force, torque, n_frames, flags), w->N,
+                     gravity_of(w), udot);
+  HIP_TRY(hipGetLastError());
+  return RSB_OK;
+}
+
 }  // namespace rsbw
 using namespace rsbw;
 
@@ -370,7 +384,7 @@ int rsb_inverse_dynamics(rsb_world* w, const float* udot, const rsb_frame* frame
   const char* who = "rsb_inverse_dynamics";
   int st = check_world(w, who, space); if (st != RSB_OK) return st;
   if (!tau && !joint_force && !joint_torque) return invalid(who, "every output is NULL");
-  st = check_loads(w, who, frames, n_frames, force, torque, flags); if (st != RSB_OK) return st;
+  st = check_dynamics_loads(w, who, frames, n_frames, force, torque, flags); if (st != RSB_OK) return st;
   HIP_TRY(hipSetDevice(w->device));
   const size_t N = (size_t)w->N, nv = (size_t)w->blob.nv, nb3 = (size_t)w->blob.nb * 3, lf = N * (size_t)n_frames * 3;
   const float *dud, *df, *dq;
@@ -390,7 +404,7 @@ int rsb_forward_dynamics(rsb_world* w, const float* tau, const rsb_frame* frames
   const char* who = "rsb_forward_dynamics";
   int st = check_world(w, who, space); if (st != RSB_OK) return st;
   if (!udot) return invalid(who, "the output is NULL");
-  st = check_loads(w, who, frames, n_frames, force, torque, flags); if (st != RSB_OK) return st;
+  st = check_dynamics_loads(w, who, frames, n_frames, force, torque, flags); if (st != RSB_OK) return st;
   HIP_TRY(hipSetDevice(w->device));
   const size_t N = (size_t)w->N, nv = (size_t)w->blob.nv, lf = N * (size_t)n_frames * 3;
   const float *dt, *df, *dq;
@@ -399,10 +413,7 @@ int rsb_forward_dynamics(rsb_world* w, const float* tau, const rsb_frame* frames
   io.in(dt, tau, N * nv); io.in(df, n_frames ? force : nullptr, lf); io.in(dq, n_frames ? torque : nullptr, lf);
   io.out(dud, udot, N * nv);
   st = io.begin(); if (st != RSB_OK) return st;
-  hipLaunchKernelGGL(aba_kernel, dim3(env_blocks(w)), dim3(kThreads), 0, stream_of(w), (const DevModel*)w->d_model, (const float*)w->d_gc, (const float*)w->d_gv,
-                     dt ? dt : (const float*)w->d_tff, n_frames ? frame_list(frames, n_frames) : FrameList{}, loads_of(w, df, dq, n_frames, flags), w->N,
-                     gravity_of(w), dud);
-  HIP_TRY(hipGetLastError());
+  st = launch_forward_dynamics(w, stream_of(w), dt, frames, n_frames, df, dq, flags, dud); if (st != RSB_OK) return st;
   return io.end();
 }
 

@@ -386,6 +386,13 @@ int diag_of(const rsb_world* w, const char* who, const float* joint_diag, Diag* 
 }
 
 }  // namespace
+
+int launch_inverse_mass_solve(rsb_world* w, hipStream_t s, int n_rhs, const float* B, float* X) {
+  hipLaunchKernelGGL(solve_kernel, dim3(env_blocks(w)), dim3(kThreads), 0, s, (const DevModel*)w->d_model, (const float*)w->d_gc, Diag{}, w->N, n_rhs, B, X);
+  HIP_TRY(hipGetLastError());
+  return RSB_OK;
+}
+
 }  // namespace rsbw
 using namespace rsbw;
 

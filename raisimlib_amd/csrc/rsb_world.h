@@ -231,6 +231,12 @@ void obs_stats_free(rsb_world* w);                                // rsb_obstats
 void frames_free(rsb_world* w);                                   // rsb_frames.hip (rsb_destroy)
 void ray_shapes_free(rsb_world* w);                               // rsb_ray_scan.hip (rsb_destroy)
 int staging(rsb_world* w, size_t floats);                       // rsb_frames.hip: d_frames_io, the staging buffer of every batched query's RSB_HOST form (Staged, frames_chain.h), at least `floats` long
+// rsb_dynamics.hip: the argument checks of the dynamics queries' loads (RSB_OK, or RSB_E_INVALID with a message naming `who`), and aba_kernel enqueued on s:
+// udot [N,nv] = FD(resident q and gv, tau (null: the resident feed-forward rows), loads), every pointer a device pointer (rsb_dynamics_derivatives.hip)
+int check_dynamics_loads(const rsb_world* w, const char* who, const rsb_frame* frames, int n_frames, const float* force, const float* torque, int flags);
+int launch_forward_dynamics(rsb_world* w, hipStream_t s, const float* tau, const rsb_frame* frames, int n_frames, const float* force, const float* torque, int flags, float* udot);
+// rsb_inverse_mass.hip: solve_kernel enqueued on s, X[e,r,:] = M(q_e)^-1 B[e,r,:] for r < n_rhs (any positive count), device pointers, X == B allowed
+int launch_inverse_mass_solve(rsb_world* w, hipStream_t s, int n_rhs, const float* B, float* X);
 // rsb_pipeline.hip
 hipStream_t stream_of(rsb_world* w);                              // the world's stream for any use other than a pipelined launch (joins first)
 int pipe_join(rsb_world* w);

@@ -774,6 +774,32 @@ class BatchedWorld:
         check(self.L.rsb_forward_dynamics(self.handle, *args, _capi.RSB_DYN_CONTACTS if contacts else 0, ptrs[0], space), "rsb_forward_dynamics")
         return res["udot"]
 
+    # -- the slopes of the two: analytic derivatives of every env in one call (rsb_dynamics_derivatives.hip) -------------------------------
+    def inverse_dynamics_derivatives(self, udot=None, loads=None, dq=True, dv=True, dudot=False, out=None):
+        """The exact derivatives of inverse_dynamics(udot, loads) at the resident state -> {"dq": [N, nv, nv] d tau_i / d x_j, "dv": [N, nv, nv]
+        d tau_i / d gv_j, "dudot": [N, nv, nv] = M(q)}, the outputs asked for only.  x is the tangent coordinate of gc in gv's order: the base
+        origin along the world axes, the base rotated about the WORLD axes (quaternion multiplied on the left), the joint coordinates.  gv,
+        udot, gravity and the loads' world force / torque are held fixed; a load's point moves with its body.  Columns 0..2 of "dq" are zero.
+        No contacts.  The world is left as it was.  out: see _frame_outputs; torch outputs take torch inputs (no synchronisation)."""
+        names = ("dq", "dv", "dudot")
+        shapes = {n: (self.N, self.nv, self.nv) for n in names}
+        space, ptrs, out = self._frame_outputs(names, dict(dq=dq, dv=dv, dudot=dudot), shapes, out, "inverse_dynamics_derivatives")
+        args, keep = self._dynamics_inputs(("udot", "inverse_dynamics_derivatives"), udot, loads, space == RSB_DEVICE)
+        check(self.L.rsb_inverse_dynamics_derivatives(self.handle, *args, 0, *ptrs, space), "rsb_inverse_dynamics_derivatives")
+        return out
+
+    def forward_dynamics_derivatives(self, tau=None, loads=None, udot=False, dq=True, dv=True, dtau=False, out=None):
+        """The exact derivatives of forward_dynamics(tau, loads) at the resident state -> {"udot": [N, nv] the forward dynamics itself, "dq":
+        [N, nv, nv] = -M^-1 d tau / d x at that udot, "dv": [N, nv, nv] = -M^-1 d tau / d gv, "dtau": [N, nv, nv] = M^-1}, the outputs asked
+        for only; the conventions of inverse_dynamics_derivatives.  With S the selection of the actuated rows, the continuous-time linearisation
+        of d/dt (x, gv) is A = [[0, I], [dq, dv]], B = [[0], [dtau S^T]].  A fixed base: rows and columns 0..5 are zero."""
+        names = ("udot", "dq", "dv", "dtau")
+        shapes = {"udot": (self.N, self.nv), **{n: (self.N, self.nv, self.nv) for n in names[1:]}}
+        space, ptrs, out = self._frame_outputs(names, dict(udot=udot, dq=dq, dv=dv, dtau=dtau), shapes, out, "forward_dynamics_derivatives")
+        args, keep = self._dynamics_inputs(("tau", "forward_dynamics_derivatives"), tau, loads, space == RSB_DEVICE)
+        check(self.L.rsb_forward_dynamics_derivatives(self.handle, *args, 0, *ptrs, space), "rsb_forward_dynamics_derivatives")
+        return out
+
     # -- inverse mass: M^-1 B and the frames' Delassus matrices of every env in one call (rsb_inverse_mass.hip) -----------------------------
     def _joint_diag(self, what, joint_diag):
         """joint_diag [nv] or None -> (C argument, what must stay alive until the call returns): always a float32 HOST array"""
