@@ -120,6 +120,29 @@ int up_quad_table(const rsb_model_blob& b, int* table) {
   return b.depth - 1;
 }
 
+// Closed form of the flat Delassus trip (step_spec.h: RSB_FLAT_DELASSUS; step_phase_delassus.inc): in a model of four consecutively numbered chains of NL = depth - 1
+// bodies, body b >= 1 sits on limb (b - 1) / NL at level (b - 1) % NL + 1, and two bodies share min(li, lj) levels of their support chains when they sit on one
+// limb, none otherwise.  Compared here, for EVERY body pair (the bodies of joint-limit rows are among them), with what the kernel's look-up gives: the number of
+// leading levels 1.. at which the two ancestor rows (build_dev_model: anc) agree.  A model the form does not describe is not reported as such chains.
+static bool delassus_closed_form_ok(const rsb_model_blob& b) {
+  const int nl = b.depth - 1;
+  if (nl < 1) return false;
+  std::vector<int> anc((size_t)b.nb * b.depth, -1);
+  for (int i = 0; i < b.nb; ++i)
+    for (int j = i; j >= 0; j = b.parent[j]) anc[(size_t)i * b.depth + b.level[j]] = j;
+  auto level_of = [&](int x) { return x > 0 ? (x - 1) % nl + 1 : 0; };
+  for (int i = 0; i < b.nb; ++i) {
+    if (level_of(i) != b.level[i]) return false;
+    for (int j = 0; j < b.nb; ++j) {
+      int table = 0;
+      while (table < nl && table + 1 <= b.level[i] && table + 1 <= b.level[j] && anc[(size_t)i * b.depth + table + 1] == anc[(size_t)j * b.depth + table + 1]) ++table;
+      const int form = (i > 0 && j > 0 && (i - 1) / nl == (j - 1) / nl) ? std::min(level_of(i), level_of(j)) : 0;
+      if (form != table) return false;
+    }
+  }
+  return true;
+}
+
 // slots of the height-map narrow phase: one per primitive (every sphere of the model may be near the ground at once - a robot lying in a hollow)
 int hm_slots_for(const rsb_model_blob& b) { return std::max(rsbk::kHmSlots, (int)b.ncol); }
 
@@ -522,7 +545,8 @@ void fill_world_args(const rsb_world* w, const LdsLayout& L, const StepClass& c,
   a.nb = w->blob.nb; a.nq = w->blob.nq; a.nv = w->blob.nv; a.ncol = w->blob.ncol; a.depth = w->blob.depth;
   a.cw = round4(6 + w->blob.depth - 1); a.max_kid = w->max_kid; a.fixed_base = w->blob.fixed_base; a.chain = (w->chain && c.lpe == 16) ? 1 : 0;
   // (2: the quad form of the up pass - its 48-float hand-over slots need the square Delassus layout's rows to themselves: the packed layout keeps the joint factors there)
-  if (a.chain && c.kmax <= 8 && up_quad_table(w->blob, nullptr) > 0 && w->blob.nb * rsbk::kUpQuadSlot <= L.ginv - L.g) a.chain = 2;
+  // (... and the flat Delassus trip takes a body's limb and level from its index: the closed form is compared with the tree tables first)
+  if (a.chain && c.kmax <= 8 && up_quad_table(w->blob, nullptr) > 0 && delassus_closed_form_ok(w->blob) && w->blob.nb * rsbk::kUpQuadSlot <= L.ginv - L.g) a.chain = 2;
   a.dt = (float)w->dt; a.gx = (float)w->gravity[0]; a.gy = (float)w->gravity[1]; a.gz = (float)w->gravity[2];
   a.mu = (float)w->mu; a.erp = (float)w->erp;
   a.alpha_init = (float)w->alpha_init; a.alpha_min = (float)w->alpha_min; a.alpha_decay = (float)w->alpha_decay;

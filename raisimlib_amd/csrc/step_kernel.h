@@ -341,6 +341,15 @@ __global__ void __launch_bounds__(64) RSB_X_WPE_ATTR rsb_step_kernel(const StepA
 #if RSB_LEAN_SEAM
 #include "step_phase_seam_setup.inc"
 #endif
+#if RSB_FLAT_DELASSUS
+  // flat Delassus trip (step_spec.h): the lane's pair s = j (j + 1) / 2 + i of the pair loop's first trip and the offsets of its two columns in WC - functions of the
+  // lane alone, formed once per launch and pinned in their registers (left alone the compiler forms them again, square root included, in every sub-step)
+  int fd_j = (int)((__builtin_sqrtf(8.0f * (float)s + 1.5f) - 1.0f) * 0.5f);   // (the pair loop's decode: step_phase_delassus.inc)
+  int fd_i = s - ((fd_j * (fd_j + 1)) >> 1);
+  int fd_wi = 3 * fd_i * cw, fd_wj = 3 * fd_j * cw;
+  int fd_ob = fd_i * GRP + kGBlock * fd_j, fd_ot = fd_j * GRP + kGBlock * fd_i, fd_og = 12 * fd_i;   // block (i, j), its transpose's place, the inverse's slot
+  asm volatile("" : "+v"(fd_i), "+v"(fd_j), "+v"(fd_wi), "+v"(fd_wj), "+v"(fd_ob), "+v"(fd_ot), "+v"(fd_og));
+#endif
 #if RSB_RESIDENT
   for (int cs = 0; cs < ncs; ++cs) {
 #endif

@@ -1,6 +1,91 @@
 // step_phase_delassus.inc — fragment of rsb_step_kernel (inside `if (ncw > 0)`): Delassus blocks G_ij = W_i W_j^T (lane = contact pair), fixed-base compliance, self-collision folding
       // ========================= Delassus blocks G_ij = W_i W_j^T (lane = contact pair) ============
+#if RSB_FLAT_CLASS
+      asm volatile("; rsb delassus begin");     // (comment lines in the assembly: tests/test_flat_delassus_host.py counts the pair loop's instructions between them)
+#endif
       const int npw = ncw * (ncw + 1) / 2;
+#if RSB_FLAT_DELASSUS
+      // flat form (step_spec.h).  The first trip - pairs 0..15: every pair of an env with at most five contacts, the only trip of the usual wave - takes (i, j) and
+      // the two columns' offsets from the lane's launch constants (step_kernel.h: fd_*); a later trip decodes its pairs at the loop's back edge, which the usual wave
+      // never takes.  ONE batch of reads by every lane - the rows of the two columns and three floats of the contact records; a lane whose pair its env does not have
+      // reads pair (0, 0) - no region, and the results of such a lane go to a sink.  Every float keeps the expression and the operand order it has in the loop
+      // of the other classes below.
+      static_assert(GROWS && !TRI && !FIXED && LPE == 16 && KMAX == 8 && RSB_SPEC_DEPTH - 1 <= ML, "flat Delassus form: the row-block layout of the floating-base quadruped classes");
+      // the sink: the 64 floats of the Delassus region behind the KMAX block rows (rsb_world.hip, make_layout_pitch: the region keeps the dense rows' 3 KMAX x (4 KMAX + 4)
+      // floats); dead from the up pass's hand-over to the seam's zeroing, read by nobody in between.  Four slots of 16 floats, taken by lane
+      static_assert(3 * KMAX * (4 * KMAX + 4) - KMAX * GRP >= 64, "flat Delassus form: the sink lies behind the block rows, inside the region");
+      float* const fsink = G + KMAX * GRP + 16 * (s & 3);
+      int fpi = fd_i, fpj = fd_j, fwi = fd_wi, fwj = fd_wj, fob = fd_ob, fot = fd_ot, fog = fd_og;
+      for (int p0 = 0;;) {
+        const bool has = fpj < nc, diag = fpi == fpj;
+        const int i = has ? fpi : 0, j = has ? fpj : 0;
+        const float* Wi = WC + (has ? fwi : 0);
+        const float* Wj = WC + (has ? fwj : 0);
+#if RSB_FLAT_SETUP_HEAD
+        constexpr int CWC = 6 + RSB_SPEC_DEPTH - 1;
+#else
+        constexpr int CWC = 6 + ML;
+#endif
+        float wi[3][CWC], wj[3][CWC];
+        RSB_UNROLL for (int rr = 0; rr < 3; ++rr) {
+          RSB_UNROLL for (int q4 = 0; q4 < (CWC + 3) / 4; ++q4) {
+            float t4[4], u4[4];
+            ld4(Wi + rr * cw + 4 * q4, t4); ld4(Wj + rr * cw + 4 * q4, u4);
+            RSB_UNROLL for (int e = 0; e < 4; ++e)
+              if (4 * q4 + e < CWC) { wi[rr][4 * q4 + e] = t4[e]; wj[rr][4 * q4 + e] = u4[e]; }
+          }
+        }
+        const float cbi = CON[i * kConSlot + 7], clim = CON[i * kConSlot + 15], cbj = CON[j * kConSlot + 7];
+        __builtin_amdgcn_sched_barrier(0);      // (the whole batch is issued before its first result is waited for)
+        // shared prefix of the two support chains.  The four chains are numbered consecutively and have NL bodies each (RSB_SPEC_UP_QUADS; the host compares this
+        // form with the tree tables for every body pair before it sets the field - rsb_world.hip: delassus_closed_form_ok): body b >= 1 sits on limb (b - 1) / NL
+        // at level (b - 1) % NL + 1, and two bodies share min(li, lj) levels on one limb, none otherwise (the base: level 0)
+        constexpr unsigned NL = RSB_SPEC_DEPTH - 1;
+        const int bi = __float_as_int(cbi), bj = __float_as_int(cbj);
+        const unsigned ui = (unsigned)(bi - 1), uj = (unsigned)(bj - 1), gi_ = ui / NL, gj_ = uj / NL;
+        const int li = bi > 0 ? (int)(ui - gi_ * NL) + 1 : 0, lj = bj > 0 ? (int)(uj - gj_ * NL) + 1 : 0;
+        const int lca = gi_ == gj_ ? min(li, lj) : 0;
+        float acc[9];
+        RSB_UNROLL for (int q2 = 0; q2 < 9; ++q2) acc[q2] = 0.f;
+        RSB_UNROLL for (int e = 0; e < CWC; ++e) {
+          const bool on = e < 6 || e < 6 + lca;
+          float av[3], bv[3];
+          RSB_UNROLL for (int rr = 0; rr < 3; ++rr) { av[rr] = on ? wi[rr][e] : 0.f; bv[rr] = on ? wj[rr][e] : 0.f; }
+          RSB_UNROLL for (int rr = 0; rr < 3; ++rr)
+            RSB_UNROLL for (int cc = 0; cc < 3; ++cc) acc[3 * rr + cc] += av[rr] * bv[cc];
+        }
+        const bool lim = diag & (clim != 0.f);   // joint-limit row: dummy tangential diagonal
+        acc[0] = lim ? 1.f : acc[0]; acc[4] = lim ? 1.f : acc[4];
+        // block (i, j) into contact i's row and its transpose into contact j's.  A diagonal pair stores the same bits to the same address twice (both sides of every
+        // product are the same column: av == bv, and a product commutes), so there is no i != j test
+        const float B[3][3] = {{acc[0], acc[1], acc[2]}, {acc[3], acc[4], acc[5]}, {acc[6], acc[7], acc[8]}};
+        const float Bt[3][3] = {{acc[0], acc[3], acc[6]}, {acc[1], acc[4], acc[7]}, {acc[2], acc[5], acc[8]}};
+        gblk_store(has ? G + fob : fsink, B);
+        gblk_store(has ? G + fot : fsink, Bt);
+        // inv3 (step_math.h) with its contractions written out as the loop below compiles them in every quadruped class - a cofactor x y - z w is fma(x, y, -(z w)),
+        // the determinant fma(A2, c2, fma(A0, c0, A1 c1)): computed by every lane, beside the stores, the compiler left ANOTHER product of the determinant unfused
+        float gi[12];
+        {
+          const float* A = acc;
+          auto cof = [](float x, float y, float z, float w) { return fmaf(x, y, -(z * w)); };
+          const float c0 = cof(A[4], A[8], A[5], A[7]), c1 = cof(A[5], A[6], A[3], A[8]), c2 = cof(A[3], A[7], A[4], A[6]);
+          const float id = 1.0f / fmaf(A[2], c2, fmaf(A[0], c0, A[1] * c1));
+          gi[0] = c0 * id; gi[1] = cof(A[2], A[7], A[1], A[8]) * id; gi[2] = cof(A[1], A[5], A[2], A[4]) * id;
+          gi[3] = c1 * id; gi[4] = cof(A[0], A[8], A[2], A[6]) * id; gi[5] = cof(A[2], A[3], A[0], A[5]) * id;
+          gi[6] = c2 * id; gi[7] = cof(A[1], A[6], A[0], A[7]) * id; gi[8] = cof(A[0], A[4], A[1], A[3]) * id;
+        }
+        gi[9] = gi[10] = gi[11] = 0.f;
+        stv<3>((has & diag) ? GINV + fog : fsink, gi);
+        p0 += LPE;
+        if (__builtin_expect(p0 >= npw, 1)) break;
+        // (more than five contacts in an env of the wave: the next sixteen pairs, decoded as in the loop below)
+        const int p = p0 + s;
+        fpj = (int)((__builtin_sqrtf(8.0f * (float)p + 1.5f) - 1.0f) * 0.5f);
+        fpi = p - ((fpj * (fpj + 1)) >> 1);
+        fwi = 3 * fpi * cw; fwj = 3 * fpj * cw;
+        fob = fpi * GRP + kGBlock * fpj; fot = fpj * GRP + kGBlock * fpi; fog = 12 * fpi;
+      }
+#else
       for (int p0 = 0; p0 < npw; p0 += LPE) {
         const int p = p0 + s;
         // pair p = j (j + 1) / 2 + i, i <= j, without the divergent search loop (up to KMAX branches of a lone wave): 8 p + 1 = (2 j + 1)^2 on the diagonal, the
@@ -82,6 +167,10 @@
           }
         }
       }
+#endif
+#if RSB_FLAT_CLASS
+      asm volatile("; rsb delassus end");
+#endif
       __syncthreads();
       if constexpr (FIXED) {   // (a class of its own: the floating-base kernels stay what they were, instruction for instruction)
         // fixed-base systems: a body fewer than three joints from the world cannot move in every direction, its contact's block

@@ -210,6 +210,37 @@ static_assert(kFlatSink >= 6 + RSB_SPEC_DEPTH - 1 && kFlatSink < kFlatCw, "flat 
 #define RSB_FLAT_SETUP_END 0
 #endif
 
+// Flat form of the Delassus phase's pair loop (step_phase_delassus.inc), in the code objects of the flat set-up that also carry RSB_SPEC_UP_QUADS (eight contact slots,
+// four consecutively numbered chains of equal length: the quadruped).  A trip of the pair loop - the first one holds every pair of an env with at most five contacts -
+// was a chain of round trips in front of the reads that matter: the two contact records' bodies, their levels, their ancestor rows, and only then the two columns'
+// rows, whose addresses depend on the pair index alone; behind the arithmetic a region each for the joint-limit diagonal (with a dependent read), the transposed
+// store and the inverse.
+//   - (i, j) of pair s of the FIRST trip, the offsets of its two columns and of its three stores are functions of the lane: formed once per launch and pinned
+//     (step_kernel.h: fd_*).  A later trip (more than five contacts in an env of the wave) decodes its pairs with the square root at the loop's back edge, which the
+//     usual wave never takes, and runs the same body: one copy of the code, so the kernel holds no more LDS instructions than it did;
+//   - ONE batch of reads by every lane: the rows of columns i and j, floats 7 and 15 of record i, float 7 of record j.  A lane whose pair its env does not have
+//     (j >= nc) reads pair (0, 0); no load sits behind a condition;
+//   - the shared prefix of the two support chains is a closed form of the two body indices: limb (b - 1) / NL, level (b - 1) % NL + 1, lca = min of the levels on one
+//     limb and 0 otherwise.  rsb_world.hip (delassus_closed_form_ok) compares the form with the parent / level tables for every body pair before it reports the
+//     model as four equal chains (StepArgs::chain == 2, the key field UP_QUADS); a model the form does not describe never gets such a code object;
+//   - the joint-limit diagonal is a select on the flag read with the batch; a diagonal pair's transposed store writes the same bits to the same address as the block
+//     itself (both operands of every product are the same column), so it has no test; every lane computes the inverse; a lane without a pair, or off the diagonal,
+//     stores to a sink: the 64 floats of the Delassus region behind the block rows.  Blocks the loop does not write stay what they were;
+//   - the inverse's contractions are written out as the loop compiles them (which product of the determinant stays unfused is the compiler's choice per context,
+//     and it chose another one for the straight form: one rounding in every inverse).
+// The self-collision fold behind the loop is what it was.
+// -DRSB_X_NO_FLAT_DELASSUS compiles the code as it was: same results bit for bit (tests/test_gpu_flat_delassus.py).  The code objects of RSB_FLAT_CLASS carry the
+// comment lines `; rsb delassus begin/end` around the pair loop, switch or not (tests/test_flat_delassus_host.py counts between them).
+// (A model of RSB_FLAT_CLASS that is not four equal chains keeps the loop: the second batch of reads such a model needs - PARLV and the two ancestor rows - is not
+//  written; no shipped workload has such a model.)
+// (The form goes with the flat set-up: -DRSB_X_NO_FLAT_SETUP compiles the set-up, the end AND the pair loop as they were - that switch's twin stays the code it was;
+//  the set-up's part switches leave the pair loop flat.)
+#if RSB_FLAT_SETUP && (RSB_I_KMAX) == 8 && RSB_SPEC_UP_QUADS && !defined(RSB_X_NO_FLAT_DELASSUS)
+#define RSB_FLAT_DELASSUS 1
+#else
+#define RSB_FLAT_DELASSUS 0
+#endif
+
 // Packed fp32 form of the contact solve's arithmetic, in the specialised code objects of the quadruped classes (16 lanes per env, eight contact slots or fewer, the
 // energy slip rule: lock-step, pipelined, resident and closed-loop).  Such a launch is one wave per SIMD, and a lone wave pays ~4 cycles for every VALU instruction
 // it issues whatever the instruction does (profiles/r02_ubench_lone_wave_latency.txt), so two fp32 operations that share an operand pattern are written as ONE
@@ -234,6 +265,8 @@ static_assert(kFlatSink >= 6 + RSB_SPEC_DEPTH - 1 && kFlatSink < kFlatCw, "flat 
 #else
 #define RSB_PK_SOLVE 0
 #endif
+// (One more part was built and is not here: a running copy of the env's normal impulses on every lane, fed by the exchange's broadcasts, in place of the sweep
+//  epilogue's row_max - same bits, and it measured nothing beside the flat Delassus form and -0.9 % without it: DESIGN.md section 9.)
 
 namespace rsbk {
 #define RSB_SPEC_COUNT_ONE(NAME, expr) +1
