@@ -236,6 +236,7 @@ int rsb_debug_phase_cycles(rsb_world* w, int enable, long long* out16);
  *  global slip searches run, Newton refinements run, contact solves (sweeps x wave contact count), cycles in searches,
  *  cycles of the solver set-up (G rows -> registers), cycles in Newton refinements, cycles in the per-sweep epilogue, 0...} */
 int rsb_debug_wave_profile(rsb_world* w, long long* out, int n_blocks);
+int rsb_debug_wave_sweep_control(rsb_world* w, long long* out, int n_blocks);   /* [12 * n_blocks]: see rsb_world.hip */
 
 
 #ifdef __cplusplus

@@ -1790,6 +1790,24 @@ int rsb_debug_wave_profile(rsb_world* w, long long* out, int n_blocks) {
   HIP_TRY(hipSetDevice(w->device));
   HIP_TRY(hipMemcpyAsync(out, w->d_prof + 16, 16 * (size_t)n_blocks * sizeof(long long), hipMemcpyDeviceToHost, stream_of(w)));
   HIP_TRY(hipStreamSynchronize(stream_of(w)));
+  // (the upper halves of words 2-7 carry the sweep-control counters: rsb_debug_wave_sweep_control)
+  for (int b = 0; b < n_blocks; ++b)
+    for (int i = 2; i < 8; ++i) out[16 * (size_t)b + i] &= 0xffffffffll;
+  return RSB_OK;
+}
+
+// per-workgroup counters of the last launch's direction refreshes, out [12 * n_blocks]: Newton blocks of first sweeps; blocks in which the one rare-path test fired
+// (or would have: the code without the test counts it too), first | later sweeps; blocks that ran the energy check, first | later; the basin check in its quad | serial
+// form; blocks followed by a global search, first | later; blocks that ran none of the three, first | later; blocks that refused a lane's step.  Saturated at 65535.
+// Counted by profiling twins compiled with -DRSB_X_SWEEP_COUNTERS (RSB_SPEC_EXTRA_DEFS) only - the counting costs a branch per counter - and zero otherwise.
+int rsb_debug_wave_sweep_control(rsb_world* w, long long* out, int n_blocks) {
+  if (!w || !out || !w->d_prof || n_blocks > w->N) return RSB_E_INVALID;
+  HIP_TRY(hipSetDevice(w->device));
+  std::vector<long long> raw(16 * (size_t)n_blocks);
+  HIP_TRY(hipMemcpyAsync(raw.data(), w->d_prof + 16, raw.size() * sizeof(long long), hipMemcpyDeviceToHost, stream_of(w)));
+  HIP_TRY(hipStreamSynchronize(stream_of(w)));
+  for (int b = 0; b < n_blocks; ++b)
+    for (int i = 0; i < 12; ++i) out[12 * (size_t)b + i] = (raw[16 * (size_t)b + 2 + i / 2] >> (32 + 16 * (i & 1))) & 0xffff;
   return RSB_OK;
 }
 

@@ -400,7 +400,9 @@ __global__ void __launch_bounds__(64) RSB_X_WPE_ATTR rsb_step_kernel(const StepA
 #include "step_phase_update.inc"
   }  // substeps
 
-  if (PROF && a.prof && lane == 0) { long long* P = a.prof + 16 + 16 * (long long)blk; P[8] = t_setup; P[9] = t_newt; P[10] = t_epi; P[11] = t_rule; P[12] = t_exch; P[13] = t_end; P[14] = t_start - t_entry; P[15] = t_mag; P[0] = clock64() - t_start; P[1] = t_gs; P[2] = p_iters; P[3] = p_ncw; P[4] = p_search; P[5] = p_newton; P[6] = p_solves; P[7] = t_srch; }
+  if (PROF && a.prof && lane == 0) { long long* P = a.prof + 16 + 16 * (long long)blk; P[8] = t_setup; P[9] = t_newt; P[10] = t_epi; P[11] = t_rule; P[12] = t_exch; P[13] = t_end; P[14] = t_start - t_entry; P[15] = t_mag; P[0] = clock64() - t_start; P[1] = t_gs; P[2] = p_iters; P[3] = p_ncw; P[4] = p_search; P[5] = p_newton; P[6] = p_solves; P[7] = t_srch;
+    // (words 2-7 are counts below 2^32: their upper halves carry the twelve sweep-control counters, 16 bits each, saturated - rsb_debug_wave_profile splits them off)
+    RSB_UNROLL for (int i = 0; i < 12; ++i) P[2 + i / 2] |= (long long)min(p_ctl[i], 0xffff) << (32 + 16 * (i & 1)); }
 #if RSB_LEAN_SEAM
   if (ls_ok && cs + 1 < ncs) {
 #include "step_phase_seam_lean.inc"

@@ -121,7 +121,17 @@
   bool dead = false;   // early termination: this env no longer integrates (its contacts at that moment stay reported)
   int nc_dead = 0;
   long long t_start = 0, t_gs = 0, t_srch = 0, t_setup = 0, t_newt = 0, t_epi = 0, t_rule = 0, t_exch = 0, t_end = 0; int p_iters = 0, p_ncw = 0, p_search = 0, p_newton = 0, p_solves = 0;
+  // (indices of p_ctl, in the order rsb_debug_wave_sweep_control reports them)
+  enum { kCtlNewtonFirst = 0, kCtlRareFirst, kCtlRareLater, kCtlEnergyFirst, kCtlEnergyLater, kCtlBasinQuad, kCtlBasinSerial, kCtlSearchFirst, kCtlSearchLater, kCtlNoneFirst, kCtlNoneLater, kCtlRefused };
+  int p_ctl[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // Newton blocks by what followed them (step_phase_solver.inc: kCtl*), profiling twin only
   if (PROF && a.prof) t_start = clock64();
+  // the sweep-control counters (p_ctl) are compiled into profiling twins that ask for them (-DRSB_X_SWEEP_COUNTERS through RSB_SPEC_EXTRA_DEFS): they count inside the
+  // blocks the stamps time, and every other twin's stamps stay what they were
+#ifdef RSB_X_SWEEP_COUNTERS
+  const bool pctl = PROF && a.prof;
+#else
+  constexpr bool pctl = false;
+#endif
   const bool pfine = PROF && a.prof && a.prof_fine;   // fine stamps: one clock read per boundary, each interval is charged to one accumulator
   long long t_prev = 0, t_mag = 0;
   auto lap = [&](long long& acc) { if (PROF && pfine) { const long long t = clock64(); acc += t - t_prev; t_prev = t; } };

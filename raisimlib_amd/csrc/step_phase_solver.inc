@@ -171,6 +171,12 @@
           sw_env = multi ? (RSB_DIM(MULTI_SW, ag.multi_stall_window) > 0 ? RSB_DIM(MULTI_SW, ag.multi_stall_window) : -1) : sw_env;
           gdw = env_groups_max<LPE>(gd);
         }
+#if RSB_SWEEP_LOOP
+        // (the pass count is wave-uniform and constant during the solve: pinned in a scalar register, or it waits in a vector register and every pass's loop test is
+        //  a vector compare)
+        gdw = __builtin_amdgcn_readfirstlane(gdw);
+        asm volatile("" : "+s"(gdw));
+#endif
         // Anderson acceleration of the sweep map (oracle: orc_params::anderson; rsb_set_solver_anderson) - the large-model classes
         // only: the quadruped's sweep loop has no register to spare and its envs converge in 3-4 sweeps.  aa_x: the impulse the sweep
         // started from; aa_g / aa_r: the previous sweep's result and residual.
@@ -305,7 +311,11 @@
           // loop's fetch-window phase: one code path for both)
           static_for<0, 5>(one);
           {
+#if RSB_SWEEP_LOOP
+            if (__builtin_expect(ncw > 5, 0)) {      // (out of line: the pass test then follows the straight part, and the next pass's rule follows the test)
+#else
             if (ncw > 5) {
+#endif
               one(std::integral_constant<int, 5>{});
               if (ncw > 6) {
                 one(std::integral_constant<int, 6>{});
@@ -401,15 +411,36 @@
 #if RSB_PK_CLASS
         asm volatile("; rsb sweep begin");     // (tests/test_pk_solve_host.py counts between the comment lines)
 #endif
+#if RSB_SWEEP_LOOP
+        // bottom-tested loops on scalar counters (step_spec.h: RSB_SWEEP_LOOP): a solve runs one sweep at least when max_iter allows any, a sweep one pass at least
+        static_assert(!(TRI || RSB_X_AA8), "sweep control: the Anderson step sits behind the exit test of the loop it replaces");
+        // What a sweep starts from - no pass run yet, no change seen, the env's live contact lanes - is set up in front of the loop and again in front of its back edge,
+        // as values the compiler cannot see through: the sweep loop's header then holds no instruction, and the back edge lands on the first pass's rule.
+        int it = 0, kp = 0;
+        float err = 0.f;
+        bool act = isc & !done;
+        asm volatile("" : "+s"(kp), "+v"(err));
+        if (max_iter > 0) for (;;) {
+#else
         for (int it = 0; it < max_iter; ++it) {
+#endif
           // lagged directions: a usable direction of this solve is no longer refreshed.  Two wave-uniform tests picked per env by a
           // lane mask (scalar work: the sweep loop has no vector register to spare)
+#if !RSB_SWEEP_LOOP
           const bool lag = multi ? (multi_fa > 0 && it >= multi_fa) : (freeze_after > 0 && it >= freeze_after);
           float err = 0.f;
+#endif
           float dl_last[3] = {0.f, 0.f, 0.f};
           if constexpr (AA) { aa_x[0] = lam[0]; aa_x[1] = lam[1]; aa_x[2] = lam[2]; }
+#if RSB_SWEEP_LOOP
+          do {
+            asm volatile("; rsb sweep control end" : "+s"(kp), "+s"(it));     // (the loop control ends where a pass's rule begins)
+            const bool lag = multi ? (multi_fa > 0 && it >= multi_fa) : (freeze_after > 0 && it >= freeze_after);      // (per pass, from the pinned counter: three scalar instructions)
+            const bool mine = act & (gpos == kp);
+#else
           for (int kp = 0; kp < gdw; ++kp) {
             const bool mine = isc & !done & (gpos == kp);
+#endif
             if (PROF && a.prof) ++p_solves;
             // v holds the velocity WITH the own impulse: lam_stick = lam - G_ii^-1 v, v_n without it = v_n - G_ii[n,:] lam
             float ls[3];
@@ -428,7 +459,11 @@
             const bool usable = (sdst == 1) & (fmaf(sc.a2, sdy, fmaf(sc.a1, sdx, sc.a0)) >= kDenFreeze * sc.a0);
             const bool keep = lag & usable;
             // who refreshes its direction in this pass: the pass's members; in an env with light passes every contact in pass 0
+#if RSB_SWEEP_LOOP
+            const bool refr = act & (light ? (kp == 0) : (gpos == kp));
+#else
             const bool refr = isc & !done & (light ? (kp == 0) : (gpos == kp));
+#endif
             bool need = refr & slip & !keep;
             // a member of a light pass keeps its direction; without a usable one (it started to slip after pass 0) it searches
             const bool lost = mine & slip & !refr & !usable;
@@ -455,9 +490,34 @@
 #endif
               // one guarded Newton step on every lane (the common case; lanes without a candidate ignore the result)
               if (PROF && a.prof) ++p_newton;
+              bool p_cont = false;      // (profiling twin: a continuation of the step ran in this block)
               float nx, ny, dstep;
 #if RSB_PK_SOLVE
-              bool ok = slip_newton_pk(kp, mu, sdx, sdy, nx, ny, dstep) & need & (sdst != 0) & (refine != 0);
+              // the Newton step's core, then ONE test for everything that may follow it (step_spec.h: RSB_SWEEP_RARE): a step above 0.02 rad of a lane that takes it
+              // (energy check), an inherited direction in the first sweep (basin check), a lane whose step was refused or that lost its direction (global search)
+              f32x2 nxy;
+              float den0, den1;
+              const bool okcore = slip_newton_core_pk(kp, sdx, sdy, nxy, dstep, den0, den1);
+              nx = nxy.x; ny = nxy.y;
+              const bool okc = okcore & need & (sdst != 0) & (refine != 0);
+#ifdef RSB_X_NO_BASIN
+              const bool rare_l = (okc & (fabsf(dstep) > 0.02f)) | (need & !okc) | lost;
+#else
+              const bool rare_l = (okc & (fabsf(dstep) > 0.02f)) | ((it == 0) & okc & (sdst == 3)) | (need & !okc) | lost;
+#endif
+              if (PROF && pctl) {      // (the twin of the code without the test counts what the test would have said)
+                if (it == 0) ++p_ctl[kCtlNewtonFirst];
+                const bool pr = __any(rare_l);
+                if (pr) ++p_ctl[it == 0 ? kCtlRareFirst : kCtlRareLater];
+                // (the energy check is counted where it runs: behind the test only where the test is compiled)
+                if ((RSB_SWEEP_RARE ? pr : true) && __any(okcore & (fabsf(dstep) > 0.02f))) { ++p_ctl[it == 0 ? kCtlEnergyFirst : kCtlEnergyLater]; p_cont = true; }
+              }
+#if RSB_SWEEP_RARE
+              bool okf = okc;
+              const bool p_rare = __any(rare_l);
+              if (__builtin_expect(p_rare, 1)) {      // (the slow block stays in line and the fast side jumps over it - hinted, so that every twin keeps this layout: out of line it costs the pipelined class's twin of the Delassus switch a spill)
+#endif
+              bool ok = slip_newton_energy_pk(kp, mu, sdx, sdy, nxy, dstep, den0, den1, okcore) & need & (sdst != 0) & (refine != 0);
 #else
               bool ok = slip_newton<COUL>(kc, mu, sdx, sdy, nx, ny, dstep) & need & (sdst != 0) & (refine != 0);
 #endif
@@ -471,6 +531,7 @@
 #endif
                 const bool chk = ok & (sdst == 3);
                 if (__any(chk)) {
+                  if (PROF && pctl) { ++p_ctl[ncw <= 4 ? kCtlBasinQuad : kCtlBasinSerial]; p_cont = true; }
                   // basin check (oracle: "basin check"): a direction inherited from the previous integrate() may sit in the
                   // local minimum the global search would not choose; it is accepted only if it is at least as good as every
                   // direction of the search's coarse scan.  Every contact lane scans the 16 directions of its OWN contact.
@@ -527,13 +588,32 @@
 #ifdef RSB_X_STAMP_BASIN
               lap(t_mag);
 #endif
+              if (PROF && pctl) { if (__any(need & (sdst != 0) & !ok)) ++p_ctl[kCtlRefused]; }
               sdx = ok ? nx : sdx; sdy = ok ? ny : sdy; sdst = ok ? 1 : sdst;
               need = (need & !ok) | lost;
               if (__any(need)) {
+                if (PROF && pctl) { ++p_ctl[it == 0 ? kCtlSearchFirst : kCtlSearchLater]; p_cont = true; }
                 for (int j = 0; j < ncw; ++j)
                   if (__any(need && s == j)) search_row(j, kc, need && s == j);
               }
+              if (PROF && pctl) { if (!p_cont) ++p_ctl[it == 0 ? kCtlNoneFirst : kCtlNoneLater]; }
               lap(t_newt);
+#if RSB_SWEEP_RARE
+                okf = false;      // (everything is taken: the selects below change nothing)
+              }
+              // the usual case comes here straight from the test: ok is okc, nobody searches - the step is taken by the selects and the pass goes on with the magnitude
+              asm volatile("; rsb refresh fast begin" : "+v"(sdx), "+v"(sdy), "+v"(sdst));     // (tests/test_sweep_control_host.py counts between the comment lines)
+              sdx = okf ? nx : sdx; sdy = okf ? ny : sdy; sdst = okf ? 1 : sdst;
+              asm volatile("; rsb refresh fast end" : "+v"(sdx), "+v"(sdy), "+v"(sdst));
+              if (PROF && pctl) { if (!p_rare) ++p_ctl[it == 0 ? kCtlNoneFirst : kCtlNoneLater]; }
+              if (PROF && pfine) { if (!p_rare) {
+#ifdef RSB_X_STAMP_BASIN
+                lap(t_newt);
+                lap(t_mag);
+#endif
+                lap(t_newt);
+              } }
+#endif
             }
             // impulse along the direction: v_n^+ = 0 on the cone boundary
             const float den = fmaf(sc.a2, sdy, fmaf(sc.a1, sdx, sc.a0));
@@ -571,7 +651,14 @@
               exchange(dl, err);
             }
             lap(t_exch);
+#if RSB_SWEEP_LOOP
+            asm volatile("; rsb sweep control begin");     // (tests/test_sweep_control_host.py follows every path from here to the comment line at the head of a pass)
+            ++kp;
+            asm volatile("" : "+s"(kp));
+          } while (__builtin_expect(kp < gdw, 0));      // (the usual env has one contact per limb: one pass per sweep, and the epilogue follows the test)
+#else
           }
+#endif
           if constexpr (AA)   // the deferred pass's share of the sweep's largest change (its members sit in the env's first row)
             err = fmaxf(err, row_max_f32(fmaxf(fabsf(dl_last[0]), fmaxf(fabsf(dl_last[1]), fabsf(dl_last[2])))));
           // an inherited direction that the first sweep did not pick up is dropped (oracle: same rule): a contact that starts
@@ -600,9 +687,25 @@
             wcount = wfull ? 0 : wcount;
             converged |= conv_now;
             done |= conv_now | stalled;
+#if RSB_SWEEP_LOOP
+            act = act & !(conv_now | stalled);      // (= isc & !done, carried: written like the set-up's it is formed in the header again)
+#endif
           }
           lap(t_epi);
+#if RSB_SWEEP_LOOP
+          // "another sweep" is one test: the lanes not yet done, none of them once the sweep count is used up
+          ++it;
+          kp = 0; err = 0.f;
+          asm volatile("" : "+s"(it), "+s"(kp), "+v"(err));
+          {
+            unsigned long long live = __builtin_amdgcn_ballot_w64(!done);
+            live = (it < max_iter) ? live : 0ull;
+            asm volatile("" : "+s"(live));      // (pinned: left alone the compiler turns the fold back into a branch of its own around the epilogue's selects)
+            if (live == 0ull) break;
+          }
+#else
           if (!__any(!done)) break;
+#endif
           if constexpr (AA) {
             if (__any(aa_on & !done)) {
               // x+ = g - gamma (g - g_prev), gamma = <r, r - r_prev> / |r - r_prev|^2 over the env's contacts (they sit in the env's

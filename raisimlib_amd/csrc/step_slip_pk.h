@@ -87,15 +87,26 @@ __device__ __forceinline__ f32x2 slip_rotate_pk(f32x2 d0, float d) { RSB_PK_NO_C
   return xy * pk_splat(inv);
 }
 
-// slip_newton (energy rule)
-__device__ __forceinline__ bool slip_newton_pk(const SlipCoefPk& k, float mu, float x0, float y0, float& x1, float& y1, float& step) { RSB_PK_NO_CONTRACT
-  const float den0 = pk_den(k, x0, y0);
+// slip_newton (energy rule) in two halves, so that the sweep loop can put the second one behind its one rare-path test (step_spec.h: RSB_SWEEP_RARE).
+// The core: den0, the step, the rotation, den1 and the four guards
+__device__ __forceinline__ bool slip_newton_core_pk(const SlipCoefPk& k, float x0, float y0, f32x2& xy, float& d, float& den0, float& den1) { RSB_PK_NO_CONTRACT
+  den0 = pk_den(k, x0, y0);
   float hp;
-  const float d = slip_newton_step_pk(k, x0, y0, den0, hp);
-  const f32x2 xy = slip_rotate_pk(f32x2{x0, y0}, d);
-  const float den1 = pk_den(k, xy.x, xy.y);
-  bool ok = (den0 > kDenNewton * k.a0) && (hp > 0.f) && (fabsf(d) <= 0.25f) && (den1 > kDenNewton * k.a0);
+  d = slip_newton_step_pk(k, x0, y0, den0, hp);
+  xy = slip_rotate_pk(f32x2{x0, y0}, d);
+  den1 = pk_den(k, xy.x, xy.y);
+  return (den0 > kDenNewton * k.a0) && (hp > 0.f) && (fabsf(d) <= 0.25f) && (den1 > kDenNewton * k.a0);
+}
+// ... and the energy check of a step above 0.02 rad (ok: the core's verdict)
+__device__ __forceinline__ bool slip_newton_energy_pk(const SlipCoefPk& k, float mu, float x0, float y0, f32x2 xy, float d, float den0, float den1, bool ok) { RSB_PK_NO_CONTRACT
   if (__any(ok && fabsf(d) > 0.02f)) ok = ok && (fabsf(d) <= 0.02f || slip_E_pk(k, mu, xy.x, xy.y, den1) <= slip_E_pk(k, mu, x0, y0, den0));
+  return ok;
+}
+__device__ __forceinline__ bool slip_newton_pk(const SlipCoefPk& k, float mu, float x0, float y0, float& x1, float& y1, float& step) { RSB_PK_NO_CONTRACT
+  f32x2 xy;
+  float d, den0, den1;
+  const bool core = slip_newton_core_pk(k, x0, y0, xy, d, den0, den1);
+  const bool ok = slip_newton_energy_pk(k, mu, x0, y0, xy, d, den0, den1, core);
   x1 = xy.x; y1 = xy.y; step = d;
   return ok;
 }

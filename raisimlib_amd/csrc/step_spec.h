@@ -268,6 +268,37 @@ static_assert(kFlatSink >= 6 + RSB_SPEC_DEPTH - 1 && kFlatSink < kFlatCw, "flat 
 // (One more part was built and is not here: a running copy of the env's normal impulses on every lane, fed by the exchange's broadcasts, in place of the sweep
 //  epilogue's row_max - same bits, and it measured nothing beside the flat Delassus form and -0.9 % without it: DESIGN.md section 9.)
 
+// Sweep control, in the code objects of the packed solve: the sweep loop's body runs about four times per sub-step in a lone wave, and every branch it holds costs
+// that wave 20-55 cycles taken or not (profiles/r02_ubench_lone_wave_latency.txt).  Two parts (step_phase_solver.inc, step_slip_pk.h):
+//   RSB_SWEEP_RARE  the direction refresh's three continuations - the energy check of a step above 0.02 rad, the basin check of an inherited direction in the first
+//                   sweep, the global search of a contact whose step was refused - sit behind ONE wave-uniform test, formed behind the Newton step's core (den0, the
+//                   step, the rotation, den1, the four guards; slip_newton_core_pk).  False, the usual case of a later sweep: the step is taken by the selects and the
+//                   pass falls through to the magnitude, no further branch, region or wait.  True: the code as it was, with its own inner tests.  The arithmetic of
+//                   both halves is untouched, and a lane that did not ask for a refresh never uses its verdict: the same bits.
+//   RSB_SWEEP_LOOP  the pass count, the pass counter and the sweep counter are pinned in scalar registers and the two loops are bottom-tested: "another pass of this
+//                   sweep" is s_cmp + s_cbranch_scc, "another sweep" one test of the lanes not yet done with the max_iter bound folded into its mask.  Between the
+//                   exchange and the next pass's rule these are the only branches of the usual path.
+// -DRSB_X_NO_SWEEP_CONTROL compiles the code as it was, -DRSB_X_NO_SWEEP_CONTROL_RARE / -DRSB_X_NO_SWEEP_CONTROL_LOOP one part of it: same results bit for bit
+// (tests/test_gpu_sweep_control.py).  The code objects of the form carry the comment lines `; rsb refresh fast begin/end` and `; rsb sweep control begin/end`
+// (tests/test_sweep_control_host.py counts between them).  Every other class compiles what it compiled.
+// -DRSB_X_SWEEP_COUNTERS compiles twelve counters into the profiling twin (what followed each Newton block, first | later sweeps: rsb_debug_wave_sweep_control,
+// tools/diag_waves.py); without it the twin's stamps time the code the other twins time.
+#if RSB_PK_SOLVE && !defined(RSB_X_NO_SWEEP_CONTROL)
+#define RSB_SWEEP_CONTROL 1
+#else
+#define RSB_SWEEP_CONTROL 0
+#endif
+#if RSB_SWEEP_CONTROL && !defined(RSB_X_NO_SWEEP_CONTROL_RARE)
+#define RSB_SWEEP_RARE 1
+#else
+#define RSB_SWEEP_RARE 0
+#endif
+#if RSB_SWEEP_CONTROL && !defined(RSB_X_NO_SWEEP_CONTROL_LOOP)
+#define RSB_SWEEP_LOOP 1
+#else
+#define RSB_SWEEP_LOOP 0
+#endif
+
 namespace rsbk {
 #define RSB_SPEC_COUNT_ONE(NAME, expr) +1
 constexpr int kSpecFields = 0 RSB_SPEC_FIELDS(RSB_SPEC_COUNT_ONE);

@@ -1204,3 +1204,11 @@ class BatchedWorld:
         out = np.zeros((nb, 16), np.int64)
         check(self.L.rsb_debug_wave_profile(self.handle, _hp(out), nb), "rsb_debug_wave_profile")
         return out
+
+    def debug_wave_sweep_control(self):
+        """[waves, 12] of the last launch: Newton blocks of first sweeps; rare-path test fired, first | later sweeps; energy check ran, first | later; basin check, quad |
+        serial form; followed by a global search, first | later; none of the three, first | later; blocks that refused a lane's step"""
+        nb = (self.N * self.lanes_per_env() + 63) // 64
+        out = np.zeros((nb, 12), np.int64)
+        check(self.L.rsb_debug_wave_sweep_control(self.handle, _hp(out), nb), "rsb_debug_wave_sweep_control")
+        return out

@@ -14,9 +14,11 @@ for cs in range(150):
     w.set_pd_target(workload.anymal_targets(N, cs), dtg); w.integrate(4); w.reset_terminated(feet, g0, v0)
 w.debug_phase_cycles(True, False)
 tot = []
+ctl = []
 for cs in range(150, 170):
     w.set_pd_target(workload.anymal_targets(N, cs), dtg); w.integrate(4)
     p = w.debug_wave_profile()
+    ctl.append(w.debug_wave_sweep_control())
     w.reset_terminated(feet, g0, v0)
     tot.append(p)
     if cs < 155:
@@ -45,3 +47,13 @@ print("GS cycles fit: const %.0f + %.0f/sweep + %.0f/contact-solve + %.0f/newton
 A2 = np.stack([np.ones_like(g), (nc >= 1) * 1.0, nc], 1).astype(np.float64)
 c2, *_ = np.linalg.lstsq(A2, (t - g).astype(np.float64), rcond=None)
 print("non-GS cycles fit: %.0f + %.0f (any contact) + %.0f per wave-max contact" % tuple(c2))
+
+# what followed the Newton blocks (rsb_debug_wave_sweep_control; step_spec.h: sweep control), first sweeps | later sweeps, per launch-wave
+C = np.concatenate(ctl).astype(np.float64)
+n1, nl = C[:, 0], nn - C[:, 0]
+rows = [("Newton blocks", n1, nl), ("rare-path test fired (or would have)", C[:, 1], C[:, 2]), ("ran the energy check", C[:, 3], C[:, 4]),
+        ("ran the basin check (quad + serial form)", C[:, 5] + C[:, 6], 0 * n1), ("followed by a global search", C[:, 7], C[:, 8]), ("none of the three", C[:, 9], C[:, 10])]
+print("(RSB_SPEC_EXTRA_DEFS=-DRSB_X_SWEEP_COUNTERS; zeros otherwise) Newton blocks per launch-wave by what followed them:  mean first sweeps | mean later sweeps | share of the later sweeps' blocks")
+for name, a, b in rows:
+    print(f"  {name:42s} {a.mean():7.3f} | {b.mean():7.3f} | {b.sum() / max(nl.sum(), 1):.3f}")
+print(f"  basin check: quad form {C[:, 5].mean():.3f}, serial form {C[:, 6].mean():.3f}; blocks that refused a lane's step {C[:, 11].mean():.3f}; launch-waves in which the test fired in no later sweep: {(C[:, 2] == 0).mean():.3f}")
