@@ -373,6 +373,26 @@ class BatchedWorld {
     std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
     RSB_CHECK(rsb_get_frame_delassus(world_, frames.data(), (int)frames.size(), angular ? RSB_DELASSUS_ANGULAR : 0, jointDiag, G, JMinv, RSB_HOST));
   }
+  /// Forward dynamics with frames HELD for all envs: (G + rho I) lambda = targetAcc - (J udot_f + Jdot gv), udot [N,dof()] = udot_f + JMinv^T lambda,
+  /// udot_f = forwardDynamics(tau), G and JMinv of getFrameDelassus(frames, angular), rho = damping * max diag G.  lambda [N,kF]: the world force
+  /// (with angular: and torque) the constraint applies at each frame; status [N]: 0 solved, RSB_HELD_SINGULAR the rows depend on each other to float
+  /// precision - lambda zero, udot = udot_f for that env (damping > 0 makes it solvable).  tau null: the feed-forward rows; targetAcc [N,kF] null:
+  /// zeros; any output may be null, not all.  Host buffers; the world is left as it was.
+  void constrainedForwardDynamics(const float* tau, const std::vector<rsb_frame>& frames, bool angular, const float* targetAcc, float damping, float* udot,
+                                  float* lambda, int32_t* status) {
+    std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
+    RSB_CHECK(rsb_constrained_forward_dynamics(world_, tau, frames.data(), (int)frames.size(), angular ? RSB_DELASSUS_ANGULAR : 0, targetAcc, damping, udot, lambda,
+                                               status, RSB_HOST));
+  }
+  /// The impulse that brings frames to targetVel [N,kF] (null: stops them) for all envs: (G + rho I) lambda = targetVel - J gv, dgv [N,dof()] =
+  /// (M + D)^-1 J^T lambda, D = diag(jointDiag) as in getFrameDelassus; lambda, status, damping as in constrainedForwardDynamics.  Nothing is written
+  /// to the world: the caller adds dgv to the generalized velocity.
+  void getFrameImpulse(const std::vector<rsb_frame>& frames, bool angular, const float* targetVel, const float* jointDiag, float damping, float* dgv, float* lambda,
+                       int32_t* status) {
+    std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
+    RSB_CHECK(rsb_frame_impulse(world_, frames.data(), (int)frames.size(), angular ? RSB_DELASSUS_ANGULAR : 0, targetVel, jointDiag, damping, dgv, lambda, status,
+                                RSB_HOST));
+  }
 
   /// HeightMap::getHeight / getNormal for ALL envs in one call, on the device, each env on its own terrain: xy [N,P,2] world coordinates ->
   /// height [N,P], normal [N,P,3] (unit normal of the triangle under the point; either may be null).  Coordinates outside the map are clamped to it;

@@ -44,6 +44,9 @@
  *   rsb_apply_inverse_mass / rsb_get_frame_delassus
  *                                       <- (new) M^-1 B and the operational-space matrices J M^-1, J M^-1 J^T at chosen frames, for all
  *                                          envs in one call, without the dense getInverseMassMatrix()
+ *   rsb_constrained_forward_dynamics / rsb_frame_impulse
+ *                                       <- (new) forward dynamics with chosen frames held and the impulse that stops them, with the
+ *                                          constraint forces and a per-env status, for all envs in one call
  *   rsb_get_terrain_height / rsb_height_scan / rsb_ray_test
  *                                       <- HeightMap::getHeight / getNormal, World::rayTest (against the terrain), for all envs
  *                                          in one call                                (HeightMap.hpp, World.hpp, absent)
@@ -492,6 +495,51 @@ int rsb_get_frame_delassus(rsb_world* w, const rsb_frame* frames, int n_frames, 
                            const float* joint_diag,      /* HOST [nv] or NULL                                            */
                            float* G,                     /* [N,kF,kF], k = 3 or 6                                        */
                            float* JMinv,                 /* [N,kF,nv]; either output may be NULL, not both               */
+                           int space);
+
+/* Frames HELD: the motion with chosen frames constrained, and the impulse that brings them to a chosen velocity, for ALL envs in one call.  With J, G
+ * and JMinv exactly those of rsb_get_frame_delassus for the same frames and flags (the same row order, m = kF rows) and
+ * rho_e = damping * max_i G_e[i][i] (damping >= 0, finite: a relative Tikhonov term; 0: none):
+ *
+ * rsb_constrained_forward_dynamics:  udot_f = rsb_forward_dynamics(tau) without loads and with flags 0 (tau NULL: the resident feed-forward rows),
+ *     a_f = J udot_f + Jdot gv, the lin_acc / ang_acc of rsb_get_frame_accelerations(udot_f) in world axes and classical form,
+ *     (G + rho I) lambda = target_acc - a_f          udot = udot_f + JMinv^T lambda          D = 0
+ *   so that J udot + Jdot gv = target_acc - rho lambda and M udot + h = tau + J^T lambda: lambda[e, 6f+a] (3f+a without RSB_DELASSUS_ANGULAR) is the
+ *   world force (a < 3) and torque (a >= 3) the constraint applies at frame f.  target_acc NULL: zeros - the frames are held.  The equations of
+ *   motion are rsb_forward_dynamics': no PD, no damping, no clips, no joint limits, no contacts; Baumgarte terms are the caller's, in target_acc.
+ * rsb_frame_impulse:  v = J gv, the lin_vel / ang_vel of rsb_get_frame_kinematics,
+ *     (G + rho I) lambda = target_vel - v            dgv = JMinv^T lambda = (M + D)^-1 J^T lambda          D = diag(joint_diag)
+ *   target_vel NULL: zeros - the frames are stopped.  It reads gc and gv and writes nothing to the world: the caller adds dgv to gv.
+ *
+ * status[e] = RSB_HELD_SOLVED (0), or RSB_HELD_SINGULAR (1): G_e + rho I is factored as a Cholesky product, and a pivot - what is left of diagonal entry
+ * i once the rows before it are taken out - was not above RSB_HELD_PIVOT_TOL (1e-5f) times that entry G_e[i][i] + rho itself, or was not finite: row i
+ * depends on the rows before it to float precision (a definition, not a measurement).  That env's lambda is then all zeros, its udot the bits of
+ * udot_f (its dgv zeros), and the call still returns RSB_OK; the other envs are not affected.  damping > 0 makes a dependent set solvable.
+ * Arithmetic: float throughout - the factorisation, the two substitutions, the sum JMinv^T lambda in row order.
+ * HIP kernels on the world's stream, like the queries above (a pipelined world is joined first); the RSB_DEVICE forms do not synchronise, the RSB_HOST
+ * forms stage through the same device buffer, which in both forms also holds udot_f, a_f or v, G and JMinv.  No bit of the world changes.  An error
+ * touches no output.  No atomics, every sum in a fixed order; env e's results depend on env e's rows alone - the same bits for any N, any subset of
+ * outputs, host or device buffers.  Fixed-base models: the base rows of udot / dgv are zero; no bit of the base entries of tau, gv and joint_diag matters.
+ * RSB_E_INVALID, with a message naming the function: a null world; a bad `space`; every output NULL; n_frames outside 1..RSB_MAX_DELASSUS_FRAMES or
+ * frames NULL; a frame whose body is out of range or whose offset is not finite; unknown flag bits; a negative or non-finite damping; for the impulse
+ * the joint_diag errors of rsb_get_frame_delassus. */
+int rsb_constrained_forward_dynamics(rsb_world* w,
+                           const float* tau,             /* [N,nv] in `space`; NULL = the resident feed-forward rows      */
+                           const rsb_frame* frames, int n_frames,   /* HOST, 1..RSB_MAX_DELASSUS_FRAMES: the held frames  */
+                           int flags,                    /* RSB_DELASSUS_ANGULAR: 6 rows per frame instead of 3          */
+                           const float* target_acc,      /* [N,kF] in `space`, rows ordered as G's; NULL = zeros         */
+                           float damping,                /* >= 0, finite, relative: rho_e = damping * max_i G_e[i][i]    */
+                           float* udot,                  /* [N,nv]                                                       */
+                           float* lambda,                /* [N,kF]                                                       */
+                           int32_t* status,              /* [N]; any output may be NULL, not all                         */
+                           int space);
+int rsb_frame_impulse(rsb_world* w, const rsb_frame* frames, int n_frames, int flags,
+                           const float* target_vel,      /* [N,kF] in `space`; NULL = zeros                              */
+                           const float* joint_diag,      /* HOST [nv] or NULL, exactly as rsb_get_frame_delassus         */
+                           float damping,
+                           float* dgv,                   /* [N,nv]  the velocity jump (M + D)^-1 J^T lambda              */
+                           float* lambda,                /* [N,kF]  the impulse                                          */
+                           int32_t* status,              /* [N]; any output may be NULL, not all                         */
                            int space);
 
 /* Terrain queries of ALL envs in one call [RECALL upstream's per-object HeightMap::getHeight / getNormal and World::rayTest, called per env on the

@@ -139,6 +139,11 @@ typedef enum rsb_scan_mode {
 #define RSB_DELASSUS_ANGULAR 1        /* flags bit 0: six rows per frame (linear 0..2, angular 3..5) instead of three */
 #define RSB_MAX_DELASSUS_FRAMES 16    /* 16 x 6 = 96 rows: G is at most 96 x 96 per env */
 
+/* Held frames (rsb_constrained_forward_dynamics, rsb_frame_impulse; rsb.h): values of `status`, and what "dependent to float precision" means */
+#define RSB_HELD_SOLVED    0
+#define RSB_HELD_SINGULAR  1          /* a pivot of the factorisation of G + rho I is not above RSB_HELD_PIVOT_TOL times its own diagonal entry, or not finite */
+#define RSB_HELD_PIVOT_TOL 1e-5f      /* a definition, not a measurement: about 100 float roundings of the entry the pivot is what is left of */
+
 /* Contact sensors (rsb_get_body_contact_wrenches, rsb_contact_observe, rsb_contact_timers; rsb.h): bits of their `flags` argument */
 #define RSB_CONTACT_LOCAL   1     /* vector outputs in the axes of the frame's body: R^T x, R = rot of rsb_get_frame_kinematics */
 #define RSB_CONTACT_NO_SELF 2     /* records flagged RSB_CONTACT_SELF_A / _B are left out (terrain contacts only) */

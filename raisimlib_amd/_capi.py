@@ -52,6 +52,7 @@ RSB_MAX_FRAMES = 64
 RSB_MAX_SCAN_POINTS = 1024
 RSB_DYN_CONTACTS = 1
 RSB_DELASSUS_ANGULAR, RSB_MAX_DELASSUS_FRAMES = 1, 16
+RSB_HELD_SOLVED, RSB_HELD_SINGULAR, RSB_HELD_PIVOT_TOL = 0, 1, 1e-5
 RSB_SCAN_WORLD, RSB_SCAN_YAW = 0, 1
 RSB_MAX_RAY_POINTS = 4096
 RSB_RAY_BODIES, RSB_RAY_OWN_BODY, RSB_RAY_PLANAR, RSB_RAY_MISS_MAX = 1, 2, 4, 8
@@ -219,6 +220,8 @@ PROTOTYPES = {
     "rsb_forward_dynamics_derivatives": (_I, [_VP, _FP, C.POINTER(Frame), _I, _FP, _FP, _I, _FP, _FP, _FP, _FP, _I]),
     "rsb_apply_inverse_mass": (_I, [_VP, _FP, _I, _FP, _FP, _I]),
     "rsb_get_frame_delassus": (_I, [_VP, C.POINTER(Frame), _I, _I, _FP, _FP, _FP, _I]),
+    "rsb_constrained_forward_dynamics": (_I, [_VP, _FP, C.POINTER(Frame), _I, _I, _FP, C.c_float, _FP, _FP, _VP, _I]),
+    "rsb_frame_impulse": (_I, [_VP, C.POINTER(Frame), _I, _I, _FP, _FP, C.c_float, _FP, _FP, _VP, _I]),
     "rsb_get_terrain_height": (_I, [_VP, _FP, _I, _FP, _FP, _I]),
     "rsb_height_scan": (_I, [_VP, C.POINTER(Frame), _I, _FP, _I, _I, _FP, C.c_longlong, _I]),
     "rsb_ray_test": (_I, [_VP, _FP, _FP, _I, C.c_float, _FP, _I]),

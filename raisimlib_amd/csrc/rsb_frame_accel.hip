@@ -145,7 +145,9 @@ __global__ __launch_bounds__(kThreads) void frame_jacobian_rates_kernel(const De
   }
 }
 
-// the launch both acceleration entry points share: exactly one of (lin_acc / ang_acc) and imu is asked for
+}  // namespace
+
+// the launch both acceleration entry points share (rsb_world.h): exactly one of (lin_acc / ang_acc) and imu is asked for
 void launch_accel(rsb_world* w, const rsb_frame* frames, int n_frames, const float* udot, int flags, float* lin_acc, float* ang_acc, float* imu,
                   long long row_stride) {
   const size_t pairs = (size_t)w->N * n_frames;
@@ -153,7 +155,6 @@ void launch_accel(rsb_world* w, const rsb_frame* frames, int n_frames, const flo
                      (const float*)w->d_gv, udot, frame_list(frames, n_frames), n_frames, w->N, gravity_of(w), flags, lin_acc, ang_acc, imu, row_stride);
 }
 
-}  // namespace
 }  // namespace rsbw
 using namespace rsbw;
 

@@ -184,6 +184,13 @@ void frames_free(rsb_world* w) {
   w->d_frames_io = nullptr; w->frames_io_cap = 0;
 }
 
+// frame_kinematics_kernel enqueued on the world's stream (rsb_world.h): device pointers, any output may be null
+void launch_frame_kinematics(rsb_world* w, const rsb_frame* frames, int n_frames, float* pos, float* rot, float* lin_vel, float* ang_vel) {
+  const size_t pairs = (size_t)w->N * n_frames;
+  hipLaunchKernelGGL(frame_kinematics_kernel, dim3(blocks_for(pairs)), dim3(kThreads), 0, stream_of(w), (const DevModel*)w->d_model, (const float*)w->d_gc,
+                     (const float*)w->d_gv, frame_list(frames, n_frames), n_frames, w->N, pos, rot, lin_vel, ang_vel);
+}
+
 }  // namespace rsbw
 using namespace rsbw;
 
@@ -200,8 +207,7 @@ int rsb_get_frame_kinematics(rsb_world* w, const rsb_frame* frames, int n_frames
   Staged io(w, space);
   io.out(dp, pos, pairs * 3); io.out(dr, rot, pairs * 9); io.out(dl, lin_vel, pairs * 3); io.out(da, ang_vel, pairs * 3);
   st = io.begin(); if (st != RSB_OK) return st;
-  hipLaunchKernelGGL(frame_kinematics_kernel, dim3(blocks_for(pairs)), dim3(kThreads), 0, stream_of(w), (const DevModel*)w->d_model, (const float*)w->d_gc,
-                     (const float*)w->d_gv, frame_list(frames, n_frames), n_frames, w->N, dp, dr, dl, da);
+  launch_frame_kinematics(w, frames, n_frames, dp, dr, dl, da);
   HIP_TRY(hipGetLastError());
   return io.end();
 }

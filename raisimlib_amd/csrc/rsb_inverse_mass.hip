@@ -387,6 +387,22 @@ int diag_of(const rsb_world* w, const char* who, const float* joint_diag, Diag* 
 
 }  // namespace
 
+int check_joint_diag(const rsb_world* w, const char* who, const float* joint_diag) {
+  Diag diag;
+  return diag_of(w, who, joint_diag, &diag);
+}
+
+int launch_frame_delassus(rsb_world* w, hipStream_t s, const rsb_frame* frames, int n_frames, int flags, const float* joint_diag, float* G, float* JMinv) {
+  Diag diag{};      // (joint_diag has passed check_joint_diag: copied, not looked at again; a fixed base's six entries stay zero)
+  for (int k = w->blob.fixed_base ? 6 : 0; joint_diag && k < w->blob.nv; ++k) diag.d[k] = joint_diag[k];
+  DelFrames fl{};
+  std::copy(frames, frames + n_frames, fl.f);
+  hipLaunchKernelGGL(delassus_kernel, dim3(env_blocks(w)), dim3(kThreads), 0, s, (const DevModel*)w->d_model, (const float*)w->d_gc, diag, w->N, fl, n_frames,
+                     (flags & RSB_DELASSUS_ANGULAR) ? 6 : 3, G, JMinv);
+  HIP_TRY(hipGetLastError());
+  return RSB_OK;
+}
+
 int launch_inverse_mass_solve(rsb_world* w, hipStream_t s, int n_rhs, const float* B, float* X) {
   hipLaunchKernelGGL(solve_kernel, dim3(env_blocks(w)), dim3(kThreads), 0, s, (const DevModel*)w->d_model, (const float*)w->d_gc, Diag{}, w->N, n_rhs, B, X);
   HIP_TRY(hipGetLastError());
@@ -424,20 +440,15 @@ int rsb_get_frame_delassus(rsb_world* w, const rsb_frame* frames, int n_frames, 
   if (!frames || n_frames < 1 || n_frames > RSB_MAX_DELASSUS_FRAMES) return invalid(who, "n_frames must be 1.." + std::to_string(RSB_MAX_DELASSUS_FRAMES));
   st = check_frames(w, who, frames, n_frames); if (st != RSB_OK) return st;
   if (flags & ~RSB_DELASSUS_ANGULAR) return invalid(who, "unknown flag bits");
-  Diag diag;
-  st = diag_of(w, who, joint_diag, &diag); if (st != RSB_OK) return st;
+  st = check_joint_diag(w, who, joint_diag); if (st != RSB_OK) return st;
   HIP_TRY(hipSetDevice(w->device));
   const int kk = (flags & RSB_DELASSUS_ANGULAR) ? 6 : 3;
   const size_t N = (size_t)w->N, rows = (size_t)kk * (size_t)n_frames;
-  DelFrames fl{};
-  std::copy(frames, frames + n_frames, fl.f);
   float *dG, *dJ;
   Staged io(w, space);      // [G | JMinv]
   io.out(dG, G, N * rows * rows); io.out(dJ, JMinv, N * rows * (size_t)w->blob.nv);
   st = io.begin(); if (st != RSB_OK) return st;
-  hipLaunchKernelGGL(delassus_kernel, dim3(env_blocks(w)), dim3(kThreads), 0, stream_of(w), (const DevModel*)w->d_model, (const float*)w->d_gc, diag, w->N, fl, n_frames, kk,
-                     dG, dJ);
-  HIP_TRY(hipGetLastError());
+  st = launch_frame_delassus(w, stream_of(w), frames, n_frames, flags, joint_diag, dG, dJ); if (st != RSB_OK) return st;
   return io.end();
 }
 

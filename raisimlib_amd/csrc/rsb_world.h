@@ -237,6 +237,15 @@ int check_dynamics_loads(const rsb_world* w, const char* who, const rsb_frame* f
 int launch_forward_dynamics(rsb_world* w, hipStream_t s, const float* tau, const rsb_frame* frames, int n_frames, const float* force, const float* torque, int flags, float* udot);
 // rsb_inverse_mass.hip: solve_kernel enqueued on s, X[e,r,:] = M(q_e)^-1 B[e,r,:] for r < n_rhs (any positive count), device pointers, X == B allowed
 int launch_inverse_mass_solve(rsb_world* w, hipStream_t s, int n_rhs, const float* B, float* X);
+// ... delassus_kernel enqueued on s: G [N,kF,kF] and JMinv [N,kF,nv] of rsb_get_frame_delassus (device pointers, either may be null) for checked frames and
+// flags; joint_diag: HOST [nv] or null, what check_joint_diag (RSB_OK, or RSB_E_INVALID with a message naming `who`) has passed
+int check_joint_diag(const rsb_world* w, const char* who, const float* joint_diag);
+int launch_frame_delassus(rsb_world* w, hipStream_t s, const rsb_frame* frames, int n_frames, int flags, const float* joint_diag, float* G, float* JMinv);
+// rsb_frame_accel.hip: frame_accel_kernel enqueued on the world's stream: the launch of rsb_get_frame_accelerations (lin_acc / ang_acc [N,F,3]) and of
+// rsb_imu_observe (imu, row_stride), device pointers; udot null: zeros.  The caller asks hipGetLastError
+void launch_accel(rsb_world* w, const rsb_frame* frames, int n_frames, const float* udot, int flags, float* lin_acc, float* ang_acc, float* imu, long long row_stride);
+// rsb_frames.hip: frame_kinematics_kernel enqueued on the world's stream: the outputs of rsb_get_frame_kinematics, device pointers, any may be null
+void launch_frame_kinematics(rsb_world* w, const rsb_frame* frames, int n_frames, float* pos, float* rot, float* lin_vel, float* ang_vel);
 // rsb_pipeline.hip
 hipStream_t stream_of(rsb_world* w);                              // the world's stream for any use other than a pipelined launch (joins first)
 int pipe_join(rsb_world* w);

@@ -850,6 +850,80 @@ class BatchedWorld:
         check(self.L.rsb_get_frame_delassus(self.handle, arr, n, _capi.RSB_DELASSUS_ANGULAR if angular else 0, dp, *ptrs, space), "rsb_get_frame_delassus")
         return out
 
+    # -- frames held: constrained forward dynamics and frame impulses of every env in one call (rsb_constrained.hip) ------------------------
+    def _held(self, what, frames, angular, tau, target, lead, want, out):
+        """the arguments both held-frame queries share (tau: None for the impulse) -> (frame array, count, flags, [tau, target] as C arguments,
+        output pointers (lead, lambda, status), space, outputs, the host arrays the pointers refer to: the caller holds them until its call returns).  Outputs as in _frame_outputs, but status is int32; inputs follow the outputs."""
+        arr, n = self._frames(frames)
+        m = (6 if angular else 3) * n
+        names = (lead, "lambda", "status")
+        shapes = {lead: (self.N, self.nv), "lambda": (self.N, m), "status": (self.N,)}
+        if out is None:
+            out = {k: np.empty(shapes[k], np.int32 if k == "status" else np.float32) for k in names if want[k]}
+        if not out:
+            raise ValueError(f"{what}: no output asked for")
+        if set(out) - set(names):
+            raise ValueError(f"{what}: unknown outputs {sorted(set(out) - set(names))}")
+        torch_like = [self._is_torch(v) for v in out.values()]
+        if any(torch_like) != all(torch_like):
+            raise ValueError(f"{what}: outputs must be all torch tensors or all numpy arrays")
+        dev = torch_like[0]
+        ptrs = []
+        for k in names:
+            v, cnt, dt = out.get(k), int(np.prod(shapes[k])), ("int32" if k == "status" else "float32")
+            if v is None:
+                ptrs.append(None)
+            elif dev:
+                if not (v.is_cuda and v.is_contiguous() and str(v.dtype) == "torch." + dt and v.numel() == cnt and v.device.index == self.device):
+                    raise ValueError(f"{what}: {k} must be a contiguous {dt} CUDA tensor of {cnt} elements on cuda:{self.device}")
+                ptrs.append(C.c_void_p(v.data_ptr()))
+            else:
+                if not (isinstance(v, np.ndarray) and v.dtype == np.dtype(dt) and v.flags.c_contiguous and v.size == cnt):
+                    raise ValueError(f"{what}: {k} must be a C-contiguous {dt} array of {cnt} elements")
+                ptrs.append(_hp(v))
+        keep, ins = [], []
+        for name, v, cnt in (("tau", tau, self.N * self.nv), ("target", target, self.N * m)):
+            if v is None:
+                ins.append(None)
+            elif dev:
+                if not (self._is_torch(v) and v.is_cuda and v.is_contiguous() and str(v.dtype) == "torch.float32" and v.numel() == cnt and v.device.index == self.device):
+                    raise ValueError(f"{what}: {name} must be a contiguous float32 CUDA tensor of {cnt} elements on cuda:{self.device}")
+                ins.append(C.c_void_p(v.data_ptr()))
+            else:
+                if self._is_torch(v):
+                    raise ValueError(f"{what}: inputs and outputs must be all torch tensors or all numpy arrays")
+                a = _host(v, np.float32)
+                if a.size != cnt:
+                    raise ValueError(f"{what}: {name} must hold {cnt} elements")
+                keep.append(a)
+                ins.append(_hp(a))
+        return arr, n, (_capi.RSB_DELASSUS_ANGULAR if angular else 0), ins, ptrs, (RSB_DEVICE if dev else RSB_HOST), out, keep
+
+    def constrained_forward_dynamics(self, frames, tau=None, angular=False, target_acc=None, damping=0.0, udot=True, lam=True, status=True, out=None):
+        """Forward dynamics with frames held, every env at once -> {"udot": [N, nv], "lambda": [N, kF], "status": [N] int32}, the outputs asked for
+        only.  With J, G, JMinv of frame_delassus(frames, angular) and rho = damping * max diag G:  (G + rho I) lambda = target_acc - (J udot_f +
+        Jdot gv), udot = udot_f + JMinv^T lambda, udot_f = forward_dynamics(tau): then J udot + Jdot gv = target_acc - rho lambda and
+        M udot + h = tau + J^T lambda.  lambda: the world force (and with angular=True torque) the constraint applies at each frame, rows ordered
+        as G's.  tau [N, nv] (None: the resident feed-forward rows); target_acc [N, kF] (None: zeros - the frames are held; Baumgarte terms go
+        here).  status 0: solved; 1 (RSB_HELD_SINGULAR): the rows are dependent to float precision (rsb.h) - that env's lambda is zero and its udot
+        is udot_f; damping > 0 makes such a set solvable.  The world is left as it was.  out: {name: float32 array (int32 for status)} or
+        {name: torch CUDA tensor} (RSB_DEVICE, no synchronisation; tau and target_acc are then torch CUDA tensors too)."""
+        what = "constrained_forward_dynamics"
+        arr, n, flags, ins, ptrs, space, out, keep = self._held(what, frames, angular, tau, target_acc, "udot", dict(udot=udot, status=status, **{"lambda": lam}), out)
+        check(self.L.rsb_constrained_forward_dynamics(self.handle, ins[0], arr, n, flags, ins[1], float(damping), *ptrs, space), "rsb_constrained_forward_dynamics")
+        return out
+
+    def frame_impulse(self, frames, angular=False, target_vel=None, joint_diag=None, damping=0.0, dgv=True, lam=True, status=True, out=None):
+        """The impulse that brings frames to target_vel [N, kF] (None: zeros - the frames are stopped), every env at once -> {"dgv": [N, nv],
+        "lambda": [N, kF], "status": [N] int32}:  (G + rho I) lambda = target_vel - J gv, dgv = (M + D)^-1 J^T lambda, G and D = diag(joint_diag)
+        as in frame_delassus, rho and status as in constrained_forward_dynamics.  gc and gv are read, nothing is written to the world: add dgv to
+        gv.  out: as in constrained_forward_dynamics."""
+        what = "frame_impulse"
+        arr, n, flags, ins, ptrs, space, out, keep = self._held(what, frames, angular, None, target_vel, "dgv", dict(dgv=dgv, status=status, **{"lambda": lam}), out)
+        dp, dkeep = self._joint_diag(what, joint_diag)
+        check(self.L.rsb_frame_impulse(self.handle, arr, n, flags, ins[1], dp, float(damping), *ptrs, space), "rsb_frame_impulse")
+        return out
+
     # -- terrain: heights, height scans and ray tests of every env in one call (rsb_terrain_query.hip) -------------------
     def _terrain_io(self, what, inputs, out_shapes, out):
         """inputs {name: (value, shape)}, out_shapes {name: shape}, out {name: array / tensor or None} -> (space, input pointers, output pointers,
