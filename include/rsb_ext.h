@@ -188,6 +188,16 @@ int rsb_model_delassus_layout(const rsb_model* m, int kmax, int self_collision, 
  * Returns the number of levels below the base and fills table[(level - 1) * 4 + quad] with the body that quad works on (table may be NULL; capacity in ints), 0 for
  * every other model (the lane = body loop runs), < 0 on error. */
 int rsb_model_up_quads(const rsb_model* m, int* table, int capacity);
+/* host only (no GPU): does the step kernel test this model's collision primitives against the plane on their own bodies' lanes (specialised code objects)?  After
+ * the down pass lane s of a 16-lane env holds the pose of body s, 1 <= s < bodies, and lane 0 and the lanes >= bodies hold the base's.  It does in a world that
+ * runs both quad forms of the tree passes (rsb_model_up_quads, <= 8 contact slots, 16 lanes per env) on the plane (terrain_type 0; 1 = height map) when the model
+ * has no rim primitive (a cylinder's end caps) and every primitive finds a (pass, lane) on a lane of its body within ceil(primitives / 16) passes: a body's
+ * primitives in index order on ascending passes, the base's over lane 0 and the lanes >= bodies of pass 0, then of pass 1 ...  Returns the number of passes and
+ * fills, per entry e = pass * 16 + lane (capacity: entries; any of the three may be NULL): prim[e] = the primitive or -1, sphere[4 e ..] = its centre in the
+ * body frame and radius, lower[e * passes + u] = bit l set where the primitive of lane l in pass u has a lower index than prim[e] (contacts are stored in
+ * primitive order: the hits among those lanes precede this one).  0 for every other model or world (the primitive-order loop runs), < 0 on error.
+ * kmax, self_collision, lanes_per_env as in rsb_model_lds_bytes. */
+int rsb_model_col_own(const rsb_model* m, int kmax, int terrain_type, int self_collision, int lanes_per_env, int* prim, int* lower, float* sphere, int capacity);
 
 /* ---- specialised step kernels.  The ahead-of-time kernel classes read the model's dimensions (bodies, coordinates, tree depth, collision primitives,
  * self-collision pairs) and the world's switches (terrain kind, sub-steps per call, warm start, solver lags) from their kernel arguments.  A SPECIALISED code

@@ -259,6 +259,7 @@ PROTOTYPES = {
     "rsb_debug_resident_full_writes": (_I, [_VP, _I]),
     "rsb_model_lds_bytes": (_I, [_VP, _I, _I, _I]),
     "rsb_model_up_quads": (_I, [_VP, _VP, _I]),
+    "rsb_model_col_own": (_I, [_VP, _I, _I, _I, _I, _VP, _VP, _VP, _I]),
     "rsb_model_delassus_layout": (_I, [_VP, _I, _I, _VP]),
     "rsb_set_specialization": (_I, [_VP, _I]),
     "rsb_specialization_status": (_I, [_VP, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),

@@ -63,6 +63,7 @@ struct rsb_world {
   uint8_t* d_tmp_mask = nullptr;
   float *d_M = nullptr, *d_h = nullptr, *d_Minv = nullptr, *d_Mwork = nullptr;
   int32_t* d_obs_idx = nullptr;
+  float* d_col_own = nullptr;          // own-lane collision table (rsb_world.hip: col_own_table; StepArgs::col_own_tab), nullptr where the model does not qualify
   int32_t* d_hm_index = nullptr;   // [N] height map of each env (rsb_set_heightmaps), NULL: all envs share map 0
   float* d_image = nullptr;           // the step kernel's per-block tables in their LDS layout (StepArgs::lds_image), rebuilt when a setter dirties it
   std::vector<float> h_kp, h_kd;      // host mirror of the PD gains (baked into the image)

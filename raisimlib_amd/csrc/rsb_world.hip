@@ -120,6 +120,41 @@ int up_quad_table(const rsb_model_blob& b, int* table) {
   return b.depth - 1;
 }
 
+// Own-lane form of the plane's collision test (step_spec.h: RSB_COL_OWN; step_phase_collision.inc).  Stage (3) of the down pass leaves the pose of body s on lane s
+// of a 16-lane env, 1 <= s < nb, and the base's on lane 0 and on the lanes >= nb.  Every collision primitive is assigned to one (pass, lane) whose lane holds the
+// primitive's body, so that the test needs no pose read: a body's primitives go in index order to ascending passes of the body's lane; the base's go in index order
+// over lane 0 and the lanes >= nb of pass 0, then over those lanes of pass 1, and so on.  A model qualifies when it has at most 16 bodies, no rim primitive
+// (rsb_model_blob::col_rim) and the assignment needs no more passes than ceil(ncol / 16), the passes of the primitive-order loop it replaces.
+// Returns the number of passes, or 0.  prim[pass * 16 + lane] = the primitive, or -1; lower[(pass * 16 + lane) * passes + u] = the lanes (bit l = lane l) whose
+// primitive of pass u has a LOWER index than prim[pass * 16 + lane] (0 where that is -1): the hits among them, over all passes u, are the contacts that precede this
+// primitive's in primitive order.  Both may be null.
+int col_own_table(const rsb_model_blob& b, int* prim, int* lower) {
+  constexpr int kLanes = 16;
+  if (b.nb < 1 || b.nb > kLanes || b.ncol < 1) return 0;
+  for (int i = 0; i < b.ncol; ++i) if (b.col_rim[i] > 0.0) return 0;
+  const int npass = (b.ncol + kLanes - 1) / kLanes;
+  std::vector<int> base_lanes(1, 0), used(b.nb, 0), P((size_t)npass * kLanes, -1);
+  for (int l = b.nb; l < kLanes; ++l) base_lanes.push_back(l);
+  for (int i = 0; i < b.ncol; ++i) {
+    const int body = b.col_body[i];
+    if (body < 0 || body >= b.nb) return 0;
+    const int k = used[body]++;
+    const int pass = body == 0 ? k / (int)base_lanes.size() : k, lane = body == 0 ? base_lanes[k % base_lanes.size()] : body;
+    if (pass >= npass) return 0;
+    P[(size_t)pass * kLanes + lane] = i;
+  }
+  for (int e = 0; e < npass * kLanes; ++e) {
+    if (prim) prim[e] = P[e];
+    if (!lower) continue;
+    for (int u = 0; u < npass; ++u) {
+      int mask = 0;
+      for (int l = 0; l < kLanes; ++l) if (P[e] >= 0 && P[(size_t)u * kLanes + l] >= 0 && P[(size_t)u * kLanes + l] < P[e]) mask |= 1 << l;
+      lower[(size_t)e * npass + u] = mask;
+    }
+  }
+  return npass;
+}
+
 // Closed form of the flat Delassus trip (step_spec.h: RSB_FLAT_DELASSUS; step_phase_delassus.inc): in a model of four consecutively numbered chains of NL = depth - 1
 // bodies, body b >= 1 sits on limb (b - 1) / NL at level (b - 1) % NL + 1, and two bodies share min(li, lj) levels of their support chains when they sit on one
 // limb, none otherwise.  Compared here, for EVERY body pair (the bodies of joint-limit rows are among them), with what the kernel's look-up gives: the number of
@@ -356,6 +391,32 @@ int launch_instance(const StepClass& c, const StepArgs& a, int blocks, size_t ld
 
 int n_self_pairs(const rsb_world* w) { return w->self_collision ? (int)w->self_pairs.size() / 2 : 0; }
 
+// the base + consecutively numbered serial chains, at most 16 bodies (StepArgs::chain)
+static bool model_is_chains(const rsb_model_blob& b) {
+  if (b.nb > 16) return false;
+  for (int i = 1; i < b.nb; ++i) if (b.level[i] >= 2 && b.parent[i] != i - 1) return false;
+  return true;
+}
+// both quad forms of the tree passes run (StepArgs::chain == 2) in the specialised code objects of class (lpe, kcap) with layout L
+static bool quad_forms_run(const rsb_model_blob& b, int lpe, int kcap, const LdsLayout& L) {
+  return model_is_chains(b) && lpe == 16 && kcap <= 8 && up_quad_table(b, nullptr) > 0 && delassus_closed_form_ok(b) && b.nb * rsbk::kUpQuadSlot <= L.ginv - L.g;
+}
+// [passes][16][kColOwnRec] as the kernel reads it (StepArgs::col_own_tab); empty where the model has no table
+static std::vector<float> col_own_image(const rsb_model_blob& b) {
+  int prim[RSB_MAX_COLLISIONS + 16], lower[(RSB_MAX_COLLISIONS + 16) * 4];
+  const int npass = b.ncol <= 64 ? col_own_table(b, prim, lower) : 0;
+  std::vector<float> img((size_t)npass * 16 * rsbk::kColOwnRec, 0.f);
+  for (int e = 0; e < npass * 16; ++e) {
+    float* r = &img[(size_t)e * rsbk::kColOwnRec];
+    const int i = prim[e];
+    if (i >= 0) { r[0] = (float)b.col_pos[i][0]; r[1] = (float)b.col_pos[i][1]; r[2] = (float)b.col_pos[i][2]; r[3] = (float)b.col_radius[i]; }
+    int words[3] = {i, 0, 0};
+    for (int u = 0; u < npass; ++u) words[1 + (u >> 1)] |= lower[e * npass + u] << (16 * (u & 1));
+    std::memcpy(r + 4, words, sizeof words);
+  }
+  return img;
+}
+
 }  // namespace rsbw
 extern "C" int rsb_model_lds_bytes(const rsb_model* m, int kmax, int self_collision, int lanes_per_env) {
   if (!m || kmax < 1 || kmax > RSB_MAX_CONTACTS || (lanes_per_env != 0 && lanes_per_env != 16 && lanes_per_env != 32 && lanes_per_env != 64)) { rsb::set_error("rsb_model_lds_bytes: bad argument"); return RSB_E_INVALID; }
@@ -380,6 +441,23 @@ extern "C" int rsb_model_up_quads(const rsb_model* m, int* table, int capacity) 
   if (table && capacity < 4 * levels) { rsb::set_error("rsb_model_up_quads: table too small"); return RSB_E_INVALID; }
   if (table) for (int i = 0; i < 4 * levels; ++i) table[i] = t[i];
   return levels;
+}
+extern "C" int rsb_model_col_own(const rsb_model* m, int kmax, int terrain_type, int self_collision, int lanes_per_env, int* prim, int* lower, float* sphere, int capacity) {
+  if (!m || kmax < 1 || kmax > RSB_MAX_CONTACTS || (lanes_per_env != 0 && lanes_per_env != 16 && lanes_per_env != 32 && lanes_per_env != 64)) { rsb::set_error("rsb_model_col_own: bad argument"); return RSB_E_INVALID; }
+  const rsb_model_blob& b = m->blob;
+  const int n_self = self_collision ? (int)rsbw::enumerate_self_pairs(b, std::vector<uint8_t>()).size() / 2 : 0;
+  const int lpe = lanes_per_env ? lanes_per_env : rsbw::default_lpe(b, kmax, n_self), kcap = rsbw::kcap_of(b, kmax);
+  const rsbk::LdsLayout L = rsbw::make_layout(b, kcap, n_self);
+  if (terrain_type != 0 || !rsbw::quad_forms_run(b, lpe, kcap, L)) return 0;
+  int p[RSB_MAX_COLLISIONS + 16], lo[(RSB_MAX_COLLISIONS + 16) * 4];
+  const int npass = rsbw::col_own_table(b, p, lo);
+  if (capacity < 16 * npass && (prim || lower || sphere)) { rsb::set_error("rsb_model_col_own: tables too small"); return RSB_E_INVALID; }
+  for (int e = 0; e < 16 * npass; ++e) {
+    if (prim) prim[e] = p[e];
+    if (lower) for (int u = 0; u < npass; ++u) lower[e * npass + u] = lo[e * npass + u];
+    if (sphere) for (int k = 0; k < 4; ++k) sphere[4 * e + k] = p[e] < 0 ? 0.f : (k < 3 ? (float)b.col_pos[p[e]][k] : (float)b.col_radius[p[e]]);
+  }
+  return npass;
 }
 namespace rsbw {
 int effective_lpe(const rsb_world* w) {
@@ -547,6 +625,9 @@ void fill_world_args(const rsb_world* w, const LdsLayout& L, const StepClass& c,
   // (2: the quad form of the up pass - its 48-float hand-over slots need the square Delassus layout's rows to themselves: the packed layout keeps the joint factors there)
   // (... and the flat Delassus trip takes a body's limb and level from its index: the closed form is compared with the tree tables first)
   if (a.chain && c.kmax <= 8 && up_quad_table(w->blob, nullptr) > 0 && delassus_closed_form_ok(w->blob) && w->blob.nb * rsbk::kUpQuadSlot <= L.ginv - L.g) a.chain = 2;
+  // own-lane form of the plane's collision test: the worlds of both quad forms, on the plane, with a table (rsb_create: the model has one)
+  a.col_own = (a.chain == 2 && w->terrain_type == 0 && w->d_col_own != nullptr) ? 1 : 0;
+  a.col_own_tab = w->d_col_own;
   a.dt = (float)w->dt; a.gx = (float)w->gravity[0]; a.gy = (float)w->gravity[1]; a.gz = (float)w->gravity[2];
   a.mu = (float)w->mu; a.erp = (float)w->erp;
   a.alpha_init = (float)w->alpha_init; a.alpha_min = (float)w->alpha_min; a.alpha_decay = (float)w->alpha_decay;
@@ -803,6 +884,13 @@ int rsb_create(const rsb_model* m, int num_envs, int device, rsb_world** out) {
   HIP_TRY(hipMalloc(&w->d_iters, N * sizeof(int32_t)));
   HIP_TRY(hipMalloc(&w->d_obs_idx, RSB_MAX_COLLISIONS * sizeof(int32_t)));
   HIP_TRY(hipMalloc(&w->d_image, (size_t)make_layout_pitch(w->blob, 8, w->blob.ncol * (w->blob.ncol - 1) / 2, rsbk::kModelPitch).shared_total * sizeof(float)));   // (room for every primitive pair)
+  {      // the own-lane collision table: the model's alone, uploaded once (fill_world_args decides per launch whether the kernel uses it)
+    const std::vector<float> own = col_own_image(w->blob);
+    if (!own.empty()) {
+      HIP_TRY(hipMalloc(&w->d_col_own, own.size() * sizeof(float)));
+      HIP_TRY(hipMemcpy(w->d_col_own, own.data(), own.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+  }
   w->self_ignore.assign((size_t)w->blob.nb * w->blob.nb, 0);
   w->self_pairs = enumerate_self_pairs(w->blob, w->self_ignore);
   w->self_mu.assign(w->self_pairs.size() / 2, -1.0); w->self_rest = w->self_mu; w->self_rthr = w->self_mu;
@@ -838,7 +926,7 @@ int rsb_destroy(rsb_world* w) {
   (void)rsb_obs_peer_destroy(w);
   void* ptrs[] = {w->d_model, w->d_gc, w->d_gv, w->d_pt, w->d_dt, w->d_tff, w->d_kp, w->d_kd, w->d_heights,
                   w->d_tmp_gc, w->d_tmp_gv, w->d_tmp_mask, w->d_M, w->d_h, w->d_Minv, w->d_Mwork, w->d_obs_idx, w->d_dbg, w->d_prof, w->d_contacts,
-                  w->d_env_mean, w->d_env_gc0, w->d_env_gv0, w->d_env_io, w->d_env_ob, w->d_env_reward, w->d_env_tau2, w->d_env_done, w->d_warm, w->d_image, w->d_self_mat, w->d_genf, w->d_hm_index, w->d_launch_mask, w->d_view_masks, w->d_cap, w->d_obs_local, w->d_obs_all,
+                  w->d_env_mean, w->d_env_gc0, w->d_env_gv0, w->d_env_io, w->d_env_ob, w->d_env_reward, w->d_env_tau2, w->d_env_done, w->d_warm, w->d_image, w->d_self_mat, w->d_genf, w->d_hm_index, w->d_launch_mask, w->d_view_masks, w->d_cap, w->d_col_own, w->d_obs_local, w->d_obs_all,
                   w->d_count, w->d_flags, w->d_iters};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (hipEvent_t e : w->ring0) (void)hipEventDestroy(e);

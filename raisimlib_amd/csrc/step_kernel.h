@@ -350,6 +350,21 @@ __global__ void __launch_bounds__(64) RSB_X_WPE_ATTR rsb_step_kernel(const StepA
   int fd_ob = fd_i * GRP + kGBlock * fd_j, fd_ot = fd_j * GRP + kGBlock * fd_i, fd_og = 12 * fd_i;   // block (i, j), its transpose's place, the inverse's slot
   asm volatile("" : "+v"(fd_i), "+v"(fd_j), "+v"(fd_wi), "+v"(fd_wj), "+v"(fd_ob), "+v"(fd_ot), "+v"(fd_og));
 #endif
+#if RSB_COL_OWN
+  // own-lane collision test (step_spec.h): this lane's primitive of every pass - local centre, radius, index (-1: none), the lower-index lanes of the passes as
+  // 16-bit masks, two to a word - is a launch constant, read by the prologue and live across the launch.  The index and the masks are pinned in their registers
+  // (the compiler otherwise re-derives the shifted masks where it likes); the four floats are left to the register allocator.  (Pinning the floats too is the same
+  // code in the plane branch, but it moved the allocation in the solver's end: the flat set-up's switch twins then spell one of their regions the other way, and
+  // tests/test_flat_setup_host.py compares those twins by mnemonic.)
+  float own_pl[kOwnPasses][3], own_rad[kOwnPasses];
+  int own_ci[kOwnPasses], own_lo[kOwnPasses][2];
+  RSB_UNROLL for (int t = 0; t < kOwnPasses; ++t) {
+    own_pl[t][0] = own_rec[t][0]; own_pl[t][1] = own_rec[t][1]; own_pl[t][2] = own_rec[t][2]; own_rad[t] = own_rec[t][3];
+    own_ci[t] = __float_as_int(own_rec[t][4]); own_lo[t][0] = __float_as_int(own_rec[t][5]); own_lo[t][1] = __float_as_int(own_rec[t][6]);
+    asm volatile("" : "+v"(own_ci[t]), "+v"(own_lo[t][0]));
+    if constexpr (kOwnPasses > 2) asm volatile("" : "+v"(own_lo[t][1]));
+  }
+#endif
 #if RSB_RESIDENT
   for (int cs = 0; cs < ncs; ++cs) {
 #endif

@@ -47,7 +47,47 @@
     if (RSB_DIM(TERRAIN, ac.terrain_type) == 0) {
       // ---- plane: depth = r - (z - z0), normal z
       const float nz[3] = {0.f, 0.f, 1.f};
-#ifdef RSB_SPECIALIZED
+#if RSB_DOWN_QUADS
+      asm volatile("; rsb plane begin");
+#endif
+#if RSB_COL_OWN
+      // Own-lane form (step_spec.h: RSB_COL_OWN): the lane's pose Rb, rb of stage (3) of the down pass IS the pose of its primitives' body, and what it tests in a
+      // pass is pinned in registers (step_kernel.h: own_*): no table read, no pose read, no rim code (the model has none).  All depth tests and ballots first; the
+      // contact's slot is the number of hits on the lanes whose primitive - of any pass - has a lower index, which is its place in primitive order.
+      {
+        constexpr int NT = kOwnPasses;
+        float pc[NT][3], pdep[NT];
+        bool phit[NT];
+        unsigned pbal[NT];
+        RSB_UNROLL for (int t = 0; t < NT; ++t) {
+          float tt[3];
+          mat3_vec(Rb, own_pl[t], tt);
+          pc[t][0] = rb[0] + tt[0]; pc[t][1] = rb[1] + tt[1]; pc[t][2] = rb[2] + tt[2];
+          pdep[t] = own_rad[t] - (pbz + pc[t][2] - ac.ground_z);
+          phit[t] = own_ci[t] >= 0 && pdep[t] > 0.f && !dead;
+        }
+        RSB_UNROLL for (int t = 0; t < NT; ++t) pbal[t] = (unsigned)(__ballot(phit[t]) >> (el * LPE)) & 0xffffu;
+        // (Stores.  The form that sent the centre of a lane without a primitive and the contact of a lane without a hit to sink slots, no exec-mask region at all,
+        //  measured BELOW these regions - eight 64-byte stores by sixteen lanes each cost more than the two skip branches: DESIGN.md section 9.)
+        RSB_UNROLL for (int t = 0; t < NT; ++t) {
+          const int ci = own_ci[t];
+          int slot = 0;
+          RSB_UNROLL for (int u = 0; u < NT; ++u) slot += __popc(pbal[u] & ((unsigned)own_lo[t][u >> 1] >> (16 * (u & 1))) & 0xffffu);
+          illegal |= phit[t] && !((ac.allowed >> (ci & 63)) & 1ull);
+          if (n_self > 0 && ci >= 0) { const float c4[4] = {pc[t][0], pc[t][1], pc[t][2], own_rad[t]}; st4(CEN + 4 * ci, c4); }
+          if (phit[t] && slot < kmax) {
+            float P[16], t1[3], t2[3];
+            contact_tangents(nz, t1, t2);
+            P[0] = pc[t][0] - own_rad[t] * nz[0]; P[1] = pc[t][1] - own_rad[t] * nz[1]; P[2] = pc[t][2] - own_rad[t] * nz[2]; P[3] = pdep[t];
+            P[4] = t1[0]; P[5] = t1[1]; P[6] = t1[2]; P[7] = __int_as_float(bb);
+            P[8] = t2[0]; P[9] = t2[1]; P[10] = t2[2]; P[11] = __int_as_float(ci);
+            P[12] = nz[0]; P[13] = nz[1]; P[14] = nz[2]; P[15] = 0.f;
+            stv<4>(CON + slot * kConSlot, P);
+          }
+        }
+        RSB_UNROLL for (int t = 0; t < NT; ++t) nc += __popc(pbal[t]);
+      }
+#elif defined(RSB_SPECIALIZED)
       // The number of passes over the primitives is a constant here: every pass's table entries are read first, then every pass's body poses, then the
       // arithmetic, then the stores (centres for the self-collision sweep, contacts).  Pass by pass - the loop below - (table entry -> body pose) is two
       // dependent LDS round trips PER PASS for the lone wave, and the stores of one pass keep the compiler from issuing the next pass's loads early.
@@ -97,6 +137,9 @@
         }
         emit(hit, ci, ci, cbody, c, rad, nz, dep);
       }
+#endif
+#if RSB_DOWN_QUADS
+      asm volatile("; rsb plane end");
 #endif
     } else {
       // ---- height map: closest feature over the cells under the sphere (oracle: terrain_contact), in three steps:

@@ -57,6 +57,15 @@
   }
   RSB_UNROLL for (int i = 0; i < 8; ++i) wrec[i] = 0.f;
   if (a.warm && s < a.kmax) ldv<2>(a.warm + (size_t)env * kWarmRow + kWarmRec * s, wrec);
+#if RSB_COL_OWN
+  // own-lane collision test (step_spec.h): what this lane tests in each pass - local centre, radius | primitive, lower-index lanes - one record per (pass, lane),
+  // read here with the launch's other global loads and pinned behind the prologue (step_kernel.h)
+  static_assert(LPE == 16 && kColOwnRec == 8, "the own-lane collision table is [passes][16 lanes][8 floats] (rsb_world.hip: col_own_image)");
+  constexpr int kOwnPasses = (RSB_SPEC_NCOL + LPE - 1) / LPE;
+  static_assert(kOwnPasses >= 1 && kOwnPasses <= 4, "the lower-index lanes of up to four passes travel in two words");
+  float own_rec[kOwnPasses][8];
+  RSB_UNROLL for (int t = 0; t < kOwnPasses; ++t) ldv<2>(a.col_own_tab + (t * LPE + s) * kColOwnRec, own_rec[t]);
+#endif
   {
     const float4* img = reinterpret_cast<const float4*>(a.lds_image);
     float4* dst = reinterpret_cast<float4*>(lds);

@@ -66,8 +66,9 @@
     bool lim_out = false;
     RSB_UNROLL for (int i = 0; i < 6; ++i) { bS[i] = 0.f; bZ[i] = 0.f; }
     RSB_UNROLL for (int i = 0; i < 10; ++i) bI10[i] = 0.f;
+    float Rb[9], rb[3];      // the lane's body pose (quad form: the base's on lane 0 and on the lanes that are no body).  Out here for the own-lane collision test (step_phase_collision.inc)
     {
-      float MF[kModelSlot], E9[9], Rb[9], rb[3], Vb[6], Ab[6];
+      float MF[kModelSlot], E9[9], Vb[6], Ab[6];
 #if RSB_SEAM_LOADS
       // (the batch issued at the top of the sub-step: one pin keeps the eight 16-byte reads whole, as below, and is the one wait for all of them.
       //  The last results of the base arithmetic are operands too: they tie the pin - the wait - BEHIND that arithmetic, which the scheduler otherwise sinks below it.)

@@ -21,7 +21,8 @@
   X(UP_QUADS, (a.chain == 2)) \
   X(MU, rsbk::spec_bits(a.mu)) X(ERP, rsbk::spec_bits(a.erp)) X(ALPHA_INIT, rsbk::spec_bits(a.alpha_init)) X(ALPHA_MIN, rsbk::spec_bits(a.alpha_min)) \
   X(ALPHA_DECAY, rsbk::spec_bits(a.alpha_decay)) X(THRESHOLD, rsbk::spec_bits(a.threshold)) X(STALL_FACTOR, rsbk::spec_bits(a.stall_factor)) \
-  X(MAX_ITER, a.max_iter)
+  X(MAX_ITER, a.max_iter) \
+  X(COL_OWN, (a.col_own != 0))
 
 #ifdef RSB_SPECIALIZED
 #define RSB_DIM(NAME, expr) (RSB_SPEC_##NAME)
@@ -73,6 +74,26 @@ constexpr float spec_f32(int bits) { return __builtin_bit_cast(float, bits); }
 #define RSB_DOWN_QUADS 1
 #else
 #define RSB_DOWN_QUADS 0
+#endif
+
+// Own-lane form of the plane's collision test (step_phase_collision.inc), in the code objects of the down pass's quad form whose world stands on the plane with a
+// model that has no rim primitive and whose every collision primitive finds a (pass, lane) on a lane of its own body (StepArgs::col_own, the key field COL_OWN;
+// rsb_world.hip: col_own_table).  Stage (3) of the down pass has just loaded Rb, rb of body s on lane s, of the base on lane 0 and on the lanes that are no body:
+// a lane tests the primitives of ITS body with that pose - pc = rb + Rb pl, mat3_vec's expression - and the phase reads neither the primitive's table entry nor a
+// body pose.  What a (pass, lane) tests - local centre, radius, primitive index, the lanes of every pass whose primitive has a lower index - is read from the
+// table once per launch (with the prologue's global loads) and pinned in registers.  Every pass's depth test and ballot come first; a contact's slot is the number
+// of hits on the lower-index lanes over all passes, so the contacts land in primitive order as before, and a slot >= kmax is dropped with flag bit 0 set.
+// The centre stores for the self-collision sweep and the contact stores keep one exec-mask region each per pass (the region-free form with sink slots measured
+// below them: DESIGN.md section 9).
+// -DRSB_X_NO_COL_OWN compiles the primitive-order loop: same results bit for bit (tests/test_gpu_col_own.py).  The code objects of the down pass's quad form carry the comment lines `; rsb plane begin/end` around the plane branch, switch or not
+// (tests/test_col_own_host.py counts between them).  The height map, a model with a cylinder and every other class compile what they compiled.
+#if RSB_DOWN_QUADS && RSB_SPEC_COL_OWN && !defined(RSB_X_NO_COL_OWN)
+#define RSB_COL_OWN 1
+#if RSB_SPEC_TERRAIN != 0
+#error "RSB_SPEC_COL_OWN: the own-lane collision test is the plane's"
+#endif
+#else
+#define RSB_COL_OWN 0
 #endif
 
 // Seam carry, for the same worlds and code objects (the classes that run both quad forms): what one sub-step's update pass leaves for the next sub-step's down pass

@@ -72,6 +72,7 @@ constexpr float kSelfReg = 1e-4f;      // == ORC_SELF_REG: compliance of a self-
 constexpr int kWarmRec = 8;           // floats per warm-state record in HBM: impulse (3), friction direction (2), direction valid, primitive + 1, pad
 constexpr int kWarmRow = kWarmRec * RSB_MAX_CONTACTS;   // floats per env row of StepArgs::warm
 constexpr int kHmRec = 28;            // floats per slot of the height-map narrow phase: sphere, cell range, 4 x 4 corner heights
+constexpr int kColOwnRec = 8;        // floats per (pass, lane) of StepArgs::col_own_tab
 constexpr int kHmSlots = 16;          // least number of slots of the height-map narrow phase (LdsLayout::hm_slots: one per primitive of the model)
 
 struct DevModel {
@@ -247,6 +248,12 @@ struct StepArgs {
   long long res_done_stride;             // bytes between their done_out rows (0: each step overwrites done_out)
   long long res_pass_global0;            // closed loop: passes served by earlier runs of this world (rsb_stage_ctx::pass_global0)
   union ResPolicy { rsb_linear_policy lin; rsb_mlp_policy mlp; } res_pol;
+  // own-lane form of the plane's collision test (step_spec.h: RSB_COL_OWN; rsb_world.hip: col_own_table).  col_own: every primitive of the model has a (pass, lane)
+  // whose lane holds the primitive's body after the down pass's quad form, the terrain is the plane, no rim primitive.  col_own_tab: [passes][16][kColOwnRec] per
+  // (pass, lane): local centre, radius | primitive (int, -1: none) | lower-index lanes of passes 0, 1 (16 bits each) | of passes 2, 3 | pad (device memory; read
+  // once per launch).  At the END of the struct: every offset the other classes read stays where it was.
+  int col_own;
+  const float* col_own_tab;
 #ifdef RSB_X_ARGPAD
   char x_pad[RSB_X_ARGPAD];
 #endif

@@ -88,6 +88,21 @@ class Model:
         check(min(n, 0), "rsb_model_up_quads")
         return [[int(t[4 * lv + g]) for g in range(4)] for lv in range(n)]
 
+    def col_own(self, kmax=8, terrain_type=0, self_collision=True, lanes_per_env=0):
+        """The (pass, lane) on which the step kernel tests every collision primitive against the plane with the pose its lane already holds, or None where the
+        primitive-order loop runs (host only; rsb_model_col_own): dict(prim [passes, 16] primitive or -1, sphere [passes, 16, 4] local centre and radius,
+        lower [passes, 16, passes] the lanes of each pass whose primitive has a lower index, as a bit mask)"""
+        import ctypes
+        import numpy as np
+        cap = 16 * 4
+        prim, lower, sphere = (ctypes.c_int * cap)(), (ctypes.c_int * (cap * 4))(), (ctypes.c_float * (cap * 4))()
+        n = lib().rsb_model_col_own(self.handle, int(kmax), int(terrain_type), int(bool(self_collision)), int(lanes_per_env), prim, lower, sphere, cap)
+        check(min(n, 0), "rsb_model_col_own")
+        if n == 0:
+            return None
+        return dict(prim=np.array(prim[:16 * n], np.int32).reshape(n, 16), sphere=np.array(sphere[:64 * n], np.float32).reshape(n, 16, 4),
+                    lower=np.array(lower[:16 * n * n], np.int32).reshape(n, 16, n))
+
     def delassus_layout(self, kmax=8, self_collision=True):
         """Where the step kernel keeps this model's Delassus blocks in an env's LDS region: dict(kcap, floats, row_pitch, block, dense_row) - block (i, k) starts
         row_pitch * i + block * k floats into the region; row_pitch 0 = the packed-triangular storage of the 16-slot classes (host only; rsb_model_delassus_layout)"""
