@@ -393,6 +393,18 @@ class BatchedWorld {
     RSB_CHECK(rsb_frame_impulse(world_, frames.data(), (int)frames.size(), angular ? RSB_DELASSUS_ANGULAR : 0, targetVel, jointDiag, damping, dgv, lambda, status,
                                 RSB_HOST));
   }
+  /// Inverse kinematics at frames (at most RSB_MAX_IK_FRAMES) for all envs: the configuration gcOut [N,gcDim()] that puts the frames at targetPos
+  /// [N,F,3] and, with targetRot [N,F,9] (row-major world <- body; null: positions only), in those orientations - rsb_inverse_kinematics' damped
+  /// Gauss-Newton iteration in float from gcInit [N,gcDim()] (null: the current state; staged view rows are uploaded first).  dofMask [dof()] (null:
+  /// the joints are free, the base is held) names the coordinates of the generalized velocity's order that may move; what is not free keeps the
+  /// start's bits.  opt: steps, damping, tolerances, step clip.  error [N,2]: the largest position and rotation row at gcOut; iterations [N];
+  /// status [N]: RSB_IK_CONVERGED, RSB_IK_MAX_ITER or RSB_IK_SINGULAR.  Any output may be null, not all.  Host buffers; the world is left as it was.
+  void inverseKinematics(const std::vector<rsb_frame>& frames, const float* targetPos, const float* targetRot, const float* gcInit, const uint8_t* dofMask,
+                         bool jointLimits, const rsb_ik_options& opt, float* gcOut, float* error, int32_t* iterations, int32_t* status) {
+    std::lock_guard<std::recursive_mutex> lk(mu_); uploadStaged();
+    RSB_CHECK(rsb_inverse_kinematics(world_, frames.data(), (int)frames.size(), (targetRot ? RSB_IK_ANGULAR : 0) | (jointLimits ? RSB_IK_JOINT_LIMITS : 0), targetPos,
+                                     targetRot, gcInit, dofMask, &opt, gcOut, error, iterations, status, RSB_HOST));
+  }
 
   /// HeightMap::getHeight / getNormal for ALL envs in one call, on the device, each env on its own terrain: xy [N,P,2] world coordinates ->
   /// height [N,P], normal [N,P,3] (unit normal of the triangle under the point; either may be null).  Coordinates outside the map are clamped to it;

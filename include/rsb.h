@@ -47,6 +47,8 @@
  *   rsb_constrained_forward_dynamics / rsb_frame_impulse
  *                                       <- (new) forward dynamics with chosen frames held and the impulse that stops them, with the
  *                                          constraint forces and a per-env status, for all envs in one call
+ *   rsb_inverse_kinematics              <- (new) the configuration that puts chosen frames at chosen places: a damped Gauss-Newton
+ *                                          iteration per env with a per-env status, for all envs in one call
  *   rsb_get_terrain_height / rsb_height_scan / rsb_ray_test
  *                                       <- HeightMap::getHeight / getNormal, World::rayTest (against the terrain), for all envs
  *                                          in one call                                (HeightMap.hpp, World.hpp, absent)
@@ -539,6 +541,52 @@ int rsb_frame_impulse(rsb_world* w, const rsb_frame* frames, int n_frames, int f
                            float damping,
                            float* dgv,                   /* [N,nv]  the velocity jump (M + D)^-1 J^T lambda              */
                            float* lambda,                /* [N,kF]  the impulse                                          */
+                           int32_t* status,              /* [N]; any output may be NULL, not all                         */
+                           int space);
+
+/* Inverse kinematics at frames: which configuration puts these frames at these places, for ALL envs in one call.  One HIP kernel on the world's
+ * stream, like the queries above (a pipelined world is joined first); the RSB_DEVICE form does not synchronise, the RSB_HOST form stages through the
+ * same device buffer.  No bit of the world changes: the iterate starts at gc_init (NULL: the resident gc) and ends in gc_out.  An error touches no output.
+ *
+ * Rows, ordered as in rsb_get_frame_delassus: k = 3 or 6 per frame, m = kF.  Row 3f+a is the position row of frame f along world axis a; with
+ * RSB_IK_ANGULAR it is row 6f+a for a < 3, and the rotation row about world axis a-3 for a >= 3.
+ * Unknowns: column d of the stacked Jacobian (gv's order: base linear, base angular, joints) takes part exactly when dof_mask[d] != 0.  dof_mask is a
+ * HOST array [nv]; NULL: every joint is free and the base is held - leg and arm IK relative to a given trunk.  Non-zero base entries free that base
+ * coordinate of a floating base; a fixed base's six entries are ignored.
+ *
+ * The iteration, in float, fixed and deterministic.  The iterate q starts at the start row (the base quaternion is normalised wherever it is read, as
+ * in every query).  At each pass, `it` counting the steps taken so far:
+ *   1. the rows e at q: position rows target_pos - pos; rotation rows the world-frame rotation vector of S = R_t R^T (R = rot of
+ *      rsb_get_frame_kinematics): v = (S21 - S12, S02 - S20, S10 - S01) / 2, c = (tr S - 1) / 2, theta = atan2(|v|, c), rows v theta / |v|, or v
+ *      itself where |v| <= 1e-6.  An angle within 1e-6 of pi has no defined axis: such targets are OUTSIDE the contract.
+ *   2. err_pos, err_rot: the largest absolute position and rotation row.  err_pos <= pos_tol and err_rot <= rot_tol: stop, RSB_IK_CONVERGED.
+ *      Otherwise, if it == max_iter: stop, RSB_IK_MAX_ITER.
+ *   3. J with masked columns zero, A = J J^T, rho = damping * max_i A[i][i]; A + rho I is factored by the root-free Cholesky with the pivot rule of
+ *      rsb_constrained_forward_dynamics (RSB_HELD_PIVOT_TOL).  A refused pivot, or max_i A[i][i] = 0: stop, RSB_IK_SINGULAR, at the current iterate.
+ *   4. y = (A + rho I)^-1 e, dq = J^T y summed in row order, in gv's coordinates; if s = max|dq| exceeds max_step, dq is scaled by max_step / s.
+ *   5. q <- q (+) dq on the free coordinates: joints add; the base origin adds; the base quaternion is multiplied on the LEFT by exp(dq[3:6]) and
+ *      normalised - the tangent convention of rsb_inverse_dynamics_derivatives.  With RSB_IK_JOINT_LIMITS the joints are then clamped into the
+ *      model's [q_lower, q_upper] (unlimited joints have none).
+ *   6. it <- it + 1.
+ * gc_out is the last iterate, error = (err_pos, err_rot) of exactly that iterate, iterations = it.  Coordinates that are not free carry the start
+ * row's bits - the base quaternion too when no base rotation is free.  max_iter == 0 is a pure evaluation: gc_out carries the start's bits.
+ * Arithmetic: float throughout; tolerances below about 1e-5 (m, rad) may never be met - the rows themselves carry float roundings of the frame
+ * positions.  No atomics, every sum in a fixed order; env e's results depend on env e's rows alone - the same bits for any N, any neighbours
+ * (converged, unconverged or singular), any subset of outputs, host or device buffers, gc_init NULL or equal to the resident rows.
+ * RSB_E_INVALID, with a message naming the function: a null world; a bad `space`; every output NULL; n_frames outside 1..RSB_MAX_IK_FRAMES or frames
+ * NULL; a frame whose body is out of range or whose offset is not finite; unknown flag bits; target_pos NULL; target_rot present without
+ * RSB_IK_ANGULAR or absent with it; opt NULL; max_iter < 0; damping, a tolerance or max_step negative or not finite; max_step == 0; a mask that
+ * frees no coordinate. */
+int rsb_inverse_kinematics(rsb_world* w, const rsb_frame* frames, int n_frames, /* HOST, 1..RSB_MAX_IK_FRAMES */
+                           int flags,                    /* RSB_IK_ANGULAR | RSB_IK_JOINT_LIMITS                         */
+                           const float* target_pos,      /* [N,F,3] world, in `space`                                    */
+                           const float* target_rot,      /* [N,F,9] row-major world<-body, in `space`; required with RSB_IK_ANGULAR, must be NULL without */
+                           const float* gc_init,         /* [N,nq] in `space`; NULL = the resident gc                    */
+                           const uint8_t* dof_mask,      /* HOST [nv] or NULL                                            */
+                           const rsb_ik_options* opt,    /* HOST                                                         */
+                           float* gc_out,                /* [N,nq]                                                       */
+                           float* error,                 /* [N,2]: largest |position row| (m), largest |rotation row| (rad; 0 without RSB_IK_ANGULAR) at gc_out */
+                           int32_t* iterations,          /* [N] steps taken                                              */
                            int32_t* status,              /* [N]; any output may be NULL, not all                         */
                            int space);
 

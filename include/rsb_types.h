@@ -144,6 +144,15 @@ typedef enum rsb_scan_mode {
 #define RSB_HELD_SINGULAR  1          /* a pivot of the factorisation of G + rho I is not above RSB_HELD_PIVOT_TOL times its own diagonal entry, or not finite */
 #define RSB_HELD_PIVOT_TOL 1e-5f      /* a definition, not a measurement: about 100 float roundings of the entry the pivot is what is left of */
 
+/* Inverse kinematics at frames (rsb_inverse_kinematics; rsb.h): the row limit, bits of `flags`, values of `status`, the options */
+#define RSB_MAX_IK_FRAMES   RSB_MAX_DELASSUS_FRAMES   /* 16: at most 96 rows */
+#define RSB_IK_ANGULAR      1     /* six rows per frame: position and orientation */
+#define RSB_IK_JOINT_LIMITS 2     /* every iterate's joints are clamped into the model's [q_lower, q_upper] */
+#define RSB_IK_CONVERGED 0
+#define RSB_IK_MAX_ITER  1
+#define RSB_IK_SINGULAR  2
+typedef struct rsb_ik_options { int32_t max_iter; float damping, pos_tol, rot_tol, max_step; } rsb_ik_options;
+
 /* Contact sensors (rsb_get_body_contact_wrenches, rsb_contact_observe, rsb_contact_timers; rsb.h): bits of their `flags` argument */
 #define RSB_CONTACT_LOCAL   1     /* vector outputs in the axes of the frame's body: R^T x, R = rot of rsb_get_frame_kinematics */
 #define RSB_CONTACT_NO_SELF 2     /* records flagged RSB_CONTACT_SELF_A / _B are left out (terrain contacts only) */

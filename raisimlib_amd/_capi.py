@@ -53,12 +53,19 @@ RSB_MAX_SCAN_POINTS = 1024
 RSB_DYN_CONTACTS = 1
 RSB_DELASSUS_ANGULAR, RSB_MAX_DELASSUS_FRAMES = 1, 16
 RSB_HELD_SOLVED, RSB_HELD_SINGULAR, RSB_HELD_PIVOT_TOL = 0, 1, 1e-5
+RSB_MAX_IK_FRAMES, RSB_IK_ANGULAR, RSB_IK_JOINT_LIMITS = 16, 1, 2
+RSB_IK_CONVERGED, RSB_IK_MAX_ITER, RSB_IK_SINGULAR = 0, 1, 2
 RSB_SCAN_WORLD, RSB_SCAN_YAW = 0, 1
 RSB_MAX_RAY_POINTS = 4096
 RSB_RAY_BODIES, RSB_RAY_OWN_BODY, RSB_RAY_PLANAR, RSB_RAY_MISS_MAX = 1, 2, 4, 8
 RSB_RAY_HIT_NONE, RSB_RAY_HIT_TERRAIN = -1, -2
 RSB_ACC_LOCAL, RSB_ACC_PROPER = 1, 2
 RSB_CONTACT_LOCAL, RSB_CONTACT_NO_SELF = 1, 2
+
+
+class IkOptions(C.Structure):
+    """rsb_ik_options"""
+    _fields_ = [("max_iter", C.c_int32), ("damping", C.c_float), ("pos_tol", C.c_float), ("rot_tol", C.c_float), ("max_step", C.c_float)]
 
 
 class TerrainProperties(C.Structure):
@@ -222,6 +229,7 @@ PROTOTYPES = {
     "rsb_get_frame_delassus": (_I, [_VP, C.POINTER(Frame), _I, _I, _FP, _FP, _FP, _I]),
     "rsb_constrained_forward_dynamics": (_I, [_VP, _FP, C.POINTER(Frame), _I, _I, _FP, C.c_float, _FP, _FP, _VP, _I]),
     "rsb_frame_impulse": (_I, [_VP, C.POINTER(Frame), _I, _I, _FP, _FP, C.c_float, _FP, _FP, _VP, _I]),
+    "rsb_inverse_kinematics": (_I, [_VP, C.POINTER(Frame), _I, _I, _FP, _FP, _FP, _VP, C.POINTER(IkOptions), _FP, _FP, _VP, _VP, _I]),
     "rsb_get_terrain_height": (_I, [_VP, _FP, _I, _FP, _FP, _I]),
     "rsb_height_scan": (_I, [_VP, C.POINTER(Frame), _I, _FP, _I, _I, _FP, C.c_longlong, _I]),
     "rsb_ray_test": (_I, [_VP, _FP, _FP, _I, C.c_float, _FP, _I]),

@@ -41,6 +41,7 @@ HOST_SOURCES = {   # source -> headers it depends on
     "rsb_dynamics.hip": _WORLD_DEPS + ["frames_chain.h"],    # batched inverse dynamics with joint reaction wrenches, contact-free forward dynamics
     "rsb_inverse_mass.hip": _WORLD_DEPS + ["frames_chain.h"],   # batched inverse-mass solves and frame Delassus matrices: one ABA factorisation per env, two passes per column
     "rsb_constrained.hip": _WORLD_DEPS + ["frames_chain.h"],    # batched forward dynamics with frames held, frame impulses: a damped Cholesky solve per env around the queries above
+    "rsb_ik.hip": _WORLD_DEPS + ["frames_chain.h"],             # batched inverse kinematics at frames: a damped Gauss-Newton iteration per env on a configuration held in LDS
     "rsb_dynamics_derivatives.hip": _WORLD_DEPS + ["frames_chain.h"],   # batched analytic derivatives of inverse and forward dynamics: forward-mode tangents of the RNEA, M^-1 by the ABA columns
     "rsb_frame_accel.hip": _WORLD_DEPS + ["frames_chain.h"], # batched frame accelerations, frame Jacobian rates and IMU readings
     "rsb_contact_sensor.hip": _WORLD_DEPS + ["frames_chain.h"],   # batched contact sensors: body wrenches, contact rows of an observation, feet air time

@@ -939,6 +939,63 @@ class BatchedWorld:
         check(self.L.rsb_frame_impulse(self.handle, arr, n, flags, ins[1], dp, float(damping), *ptrs, space), "rsb_frame_impulse")
         return out
 
+    # -- inverse kinematics at frames: the configuration that puts frames at chosen places, every env in one call (rsb_ik.hip) ----------------
+    def inverse_kinematics(self, frames, target_pos, target_rot=None, gc_init=None, dof_mask=None, joint_limits=False, max_iter=20, damping=1e-3,
+                           pos_tol=1e-4, rot_tol=1e-4, max_step=0.5, gc=True, error=True, iterations=True, status=True, out=None):
+        """The configuration that puts frames at target_pos [N, F, 3] (and, with target_rot [N, F, 9] row-major world<-body, in those orientations),
+        every env at once -> {"gc": [N, nq], "error": [N, 2] (largest position row [m], largest rotation row [rad]) at gc, "iterations": [N] int32,
+        "status": [N] int32}, the outputs asked for only.  A damped Gauss-Newton iteration in float from gc_init [N, nq] (None: the resident gc):
+        (J J^T + damping max diag I) y = e, dq = J^T y clipped to max_step, q (+) dq with the base quaternion multiplied on the left (rsb.h states
+        every step).  dof_mask [nv] (host; None: the joints are free, the base is held): the coordinates of gv's order that may move; what is not
+        free keeps the start's bits.  joint_limits=True clamps every iterate's joints into the model's limits.  status 0: within pos_tol / rot_tol;
+        1 (RSB_IK_MAX_ITER): max_iter steps taken; 2 (RSB_IK_SINGULAR): the rows depend on each other to float precision and damping is too small.
+        max_iter=0 evaluates the start.  The world is left as it was.  out: {name: float32 array (int32 for iterations, status)} or {name: torch
+        CUDA tensor} (RSB_DEVICE, no synchronisation; the targets and gc_init are then torch CUDA tensors too)."""
+        what = "inverse_kinematics"
+        arr, n = self._frames(frames)
+        names = ("gc", "error", "iterations", "status")
+        shapes = {"gc": (self.N, self.nq), "error": (self.N, 2), "iterations": (self.N,), "status": (self.N,)}
+        dtypes = {"gc": "float32", "error": "float32", "iterations": "int32", "status": "int32"}
+        if out is None:
+            want = dict(gc=gc, error=error, iterations=iterations, status=status)
+            out = {k: np.empty(shapes[k], dtypes[k]) for k in names if want[k]}
+        if not out:
+            raise ValueError(f"{what}: no output asked for")
+        if set(out) - set(names):
+            raise ValueError(f"{what}: unknown outputs {sorted(set(out) - set(names))}")
+        torch_like = [self._is_torch(v) for v in out.values()]
+        if any(torch_like) != all(torch_like):
+            raise ValueError(f"{what}: outputs must be all torch tensors or all numpy arrays")
+        dev = torch_like[0]
+        ptrs = [self._sensor_buffer(what, k, out.get(k), dtypes[k], int(np.prod(shapes[k])), dev) for k in names]
+        keep, ins = [], []
+        for name, v, cnt in (("target_pos", target_pos, self.N * n * 3), ("target_rot", target_rot, self.N * n * 9), ("gc_init", gc_init, self.N * self.nq)):
+            if v is None:
+                ins.append(None)
+            elif dev:
+                ins.append(self._sensor_buffer(what, name, v, "float32", cnt, True))
+            else:
+                if self._is_torch(v):
+                    raise ValueError(f"{what}: inputs and outputs must be all torch tensors or all numpy arrays")
+                a = _host(v, np.float32)
+                if a.size != cnt:
+                    raise ValueError(f"{what}: {name} must hold {cnt} elements")
+                keep.append(a)
+                ins.append(_hp(a))
+        mp = None
+        if dof_mask is not None:
+            if self._is_torch(dof_mask):
+                dof_mask = dof_mask.detach().cpu().numpy()
+            mk = np.ascontiguousarray(np.asarray(dof_mask) != 0, np.uint8)
+            if mk.size != self.nv:
+                raise ValueError(f"{what}: dof_mask must hold {self.nv} elements")
+            keep.append(mk)
+            mp = _hp(mk)
+        opt = _capi.IkOptions(int(max_iter), float(damping), float(pos_tol), float(rot_tol), float(max_step))
+        flags = (_capi.RSB_IK_ANGULAR if target_rot is not None else 0) | (_capi.RSB_IK_JOINT_LIMITS if joint_limits else 0)
+        check(self.L.rsb_inverse_kinematics(self.handle, arr, n, flags, *ins, mp, C.byref(opt), *ptrs, RSB_DEVICE if dev else RSB_HOST), "rsb_inverse_kinematics")
+        return out
+
     # -- terrain: heights, height scans and ray tests of every env in one call (rsb_terrain_query.hip) -------------------
     def _terrain_io(self, what, inputs, out_shapes, out):
         """inputs {name: (value, shape)}, out_shapes {name: shape}, out {name: array / tensor or None} -> (space, input pointers, output pointers,
